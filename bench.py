@@ -3,11 +3,14 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a torchrun environment: starts its own N ranks as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py ... --full                          (+ the secondary measurements: idle-stream host cost, full step, kernel probes, CPU baseline)
+    python bench.py ... --dump-outputs DIR              (+ what the last timed step computed, as DIR/<name>.npy)
 
 A "step" = student forward (a1-a13) + fused matching loss (a14) + full backward to every parameter gradient
 (+ bucketed RCCL gradient all-reduce when N > 1) on ONE batch of 32 synthetic 16x224^2 clips per GPU, bf16 storage with
 fp32 accumulation, inputs resident in HBM before the timed region.  Teacher scene logits are an input tensor
-(primary metric of SURVEY.md §8d).  Rank 0 prints ONE JSON line.
+(primary metric of SURVEY.md §8d).  Rank 0 prints ONE JSON line.  Without --full a run does only what that line's headline
+needs: set-up, W warm-up steps, K timed steps (and the dump when asked for).
 """
 from __future__ import annotations
 
@@ -55,7 +58,14 @@ def parse():
     ap.add_argument("--reserve-cus", type=int, default=0, help="persistent GEMM grids leave this many CUs free (library option gemm_reserve_cus)")
     ap.add_argument("--cu-hog-us", type=int, default=0, help="how long each --cu-hog workgroup holds its CU; 0 (default) = 90 %% of the backward's device time, measured in two un-hogged steps "
                                                                "(a longer hold than the backward makes the step wait for the hog, not for its work: round 6 found the old fixed 36 ms doing that)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the host cost of one step on an idle stream, the secondary full step, the kernel "
+                    "probes and the CPU baseline (--no-full-step, --no-probes, --no-cpu-baseline leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (losses, logits, model outputs, every parameter "
+                    "gradient) as DIR/<name>.npy, float32 / float64; arrays beyond their share of 64 MB as a fixed seeded sample")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def build_model(args, device):
@@ -334,6 +344,35 @@ def self_launch(args) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files together
+
+
+def dump_outputs(path: str, total, out, logits, loss_terms, model) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, one PATH/<name>.npy per array -- the total loss and every loss term (float64), the loss's
+    logits, the model's outputs and every parameter gradient (float32).  An array of more than DUMP_BYTES / 8 / (number of arrays) elements is written as a
+    sample of its flattened elements whose indices depend only on its size (seed 0), so runs with the same arguments write the same elements."""
+    import numpy as np
+    (action_feat, scene_feat), (action_logit, scene_logit, attn), (slots_head, slots, mask_predictions) = out
+    arrays = {"loss.total": total, **{f"loss.{k}": v for k, v in loss_terms.items()}, "logits": logits,
+              "out.action_feat": action_feat, "out.scene_feat": scene_feat, "out.action_logit": action_logit, "out.scene_logit": scene_logit,
+              "out.attn": attn, "out.slots_head": slots_head, "out.slots": slots, "out.mask_predictions": mask_predictions}
+    arrays.update({f"grad.{n}": p.grad for n, p in model.named_parameters() if p.grad is not None})
+    cap = DUMP_BYTES // 8 // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    written, sampled, picks = 0, 0, {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.numel() > cap:
+            if t.numel() not in picks:
+                picks[t.numel()] = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values.to(t.device)
+            t = t.reshape(-1)[picks[t.numel()]]
+            sampled += 1
+        a = t.to(torch.float64 if name.startswith("loss") else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": path, "arrays": len(arrays), "sampled": sampled, "bytes": written}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -394,7 +433,7 @@ def main():
             bw.append(eb0.elapsed_time(eb1))
         args.cu_hog_us = int(0.9 * min(bw) * 1e3)
 
-    def step():
+    def step(keep=None):
         for p in model.parameters():
             p.grad = None
         out = model(x)
@@ -407,19 +446,22 @@ def main():
             sync.finish()
         if hog_stream is not None:
             torch.cuda.current_stream(device).wait_stream(hog_stream)
+        if keep is not None:                           # (the last timed step only: what --dump-outputs writes)
+            keep.update(out=out, logits=logits, loss_terms=ld)
         return total
 
     for _ in range(args.warmup):
-        loss = step()
+        step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    last = {}
     _dl.CALLS[0] = 0
     t0 = time.perf_counter()
     e0.record()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(last if i == args.steps - 1 else None)
     e1.record()
     host_enqueue = time.perf_counter() - t0          # host time to ENQUEUE the K steps (the device is still running): launch-bound check
     lib_calls = _dl.CALLS[0] / args.steps              # host -> library compute calls per step (one per fused region and direction)
@@ -433,16 +475,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = float(t)
     loss_value = float(loss.detach().float().sum())
-    # host cost of a step: ONE step enqueued on an idle stream (in the back-to-back loop above the launch queue fills up and the host is throttled
-    # to the device's pace, so that number says nothing about the host); median of 5, outside the timed region
+    dumped = dump_outputs(args.dump_outputs, loss, last["out"], last["logits"], last["loss_terms"], model) if args.dump_outputs and rank == 0 else None
+    del last
     host_idle = []
-    for _ in range(5):
+    if args.full:
+        # host cost of a step: ONE step enqueued on an idle stream (in the back-to-back loop above the launch queue fills up and the host is throttled
+        # to the device's pace, so that number says nothing about the host); median of 5, outside the timed region
+        for _ in range(5):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            step()
+            host_idle.append(time.perf_counter() - th)
         torch.cuda.synchronize()
-        th = time.perf_counter()
-        step()
-        host_idle.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    host_idle.sort()
+        host_idle.sort()
     rccl_info = rank_proof(f"{torch.cuda.get_device_name(device)} (cuda:{device.index})") if world > 1 else None
     if rank != 0:
         if world > 1:
@@ -450,7 +495,7 @@ def main():
         return
 
     full = None
-    if not args.no_full_step and world == 1:
+    if args.full and not args.no_full_step and world == 1:
         # secondary number: the same step + frozen teacher forward (a15) + fused AdamW update (a18)
         from devias_amd.modeling_finetune import vit_base_patch16_224
         from devias_amd.optim import FusedAdamW
@@ -514,15 +559,20 @@ def main():
         # roofline.sustained_peak / frac_of_sustained; `rccl` at N > 1.  schema 4 (round 4): `host_enqueue_ms_per_step` has its round-1/2 meaning again (host time to enqueue the K timed steps back to back: a full launch
         # queue throttles the host to the device's pace, so on a device-bound step it reads ~ the step time); the host's own cost is the idle-stream number
         # schema 6 (round 6): roofline.gemm_shapes = every GEMM of an encoder block timed inside a real step (one armed step per signature)
-        "schema": 6,
+        # schema 7: host_idle_*, full_step, the kernel probes of `roofline` and cpu_baseline only with --full; `outputs` with --dump-outputs
+        "schema": 7, "full": args.full,
         "host_enqueue_ms_per_step": host_enqueue / args.steps * 1e3, "host_library_calls_per_step": lib_calls,
-        "host_idle_enqueue_ms_per_step": host_idle[len(host_idle) // 2] * 1e3,
-        "host_idle_enqueue_method": "one step enqueued on an idle stream, median of 5, outside the timed region (python + fused-region library calls + HIP launches)",
         "device_ms_per_step": dev_ms / args.steps, "final_loss": loss_value, "peak_mem_gib": peak_mem,
     }
-    if ach is not None and args.no_probes:
+    if host_idle:
+        line["host_idle_enqueue_ms_per_step"] = host_idle[len(host_idle) // 2] * 1e3
+        line["host_idle_enqueue_method"] = "one step enqueued on an idle stream, median of 5, outside the timed region (python + fused-region library calls + HIP launches)"
+    if dumped is not None:
+        line["outputs"] = dumped
+    if ach is not None and (args.no_probes or not args.full):
         line["roofline"] = {"bound": "mfma", "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS, "traffic": None,
-                            "scope": f"whole step per GPU: {gflop} algorithmic GFLOP/clip x {B} clips / step time", "note": "--no-probes: kernel probes skipped"}
+                            "scope": f"whole step per GPU: {gflop} algorithmic GFLOP/clip x {B} clips / step time",
+                            "note": "--no-probes: kernel probes skipped" if args.full else "kernel probes run with --full only"}
     elif ach is not None:
         in_step = step if world == 1 else None            # (at N > 1 a step contains collectives: rank 0 cannot run one alone)
         dom = trace_top_kernel_probe(args, device, in_step)
@@ -542,9 +592,9 @@ def main():
         line["rccl"] = rccl_info
     if full is not None:
         line["full_step"] = full
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args)
-    elif world > 1:
+    elif args.full and world > 1:
         line["cpu_baseline"] = None
         line["cpu_baseline_note"] = "reported by the N = 1 run only (rank 0's host cores are shared with the other ranks' launch threads at N > 1)"
     print(json.dumps(line))
