@@ -2163,7 +2163,8 @@ struct GemmKnobs {
     int aux_nt;        // "gemm_aux_nt"     DEVIAS_GEMM_AUX_NT   5 (default): bit 0: the persistent kernels store the saved pre-activation of a GELU epilogue non-temporally -- nobody reads it before the backward --, bit 2: that launch's first output too (fc1; together -0.4 ... -0.5 ms per step, in-process A/B)
     int smallm;        // "gemm_smallm"     DEVIAS_GEMM_SMALLM   1 (default): bf16 products with M <= 128 and B k-contiguous run on gemm_smallm_kernel (one launch, no split-K), a workgroup per 16-row tile where there are few column groups; 2: one workgroup per column group always (A/B aid)
     int tail_split;    // "gemm_tail_split" DEVIAS_GEMM_TAIL_SPLIT  eight-wave persistent kernel: last partial round's tiles as 128-row halves on two workgroups (1), whose idle waves
-                       //                                        also skip the LDS-DMA of the A rows nobody multiplies (2, default); 0 = whole tiles
+                       //                                        also skip the LDS-DMA of the A rows nobody multiplies (2); 3 (default) / 4: up to thirds / quarters where
+                       //                                        the launch allows (static tile lists, no column sums, B k-contiguous: else halves); 0 = whole tiles.  Every value: same bits
     int w4;            // "gemm_w4"         DEVIAS_GEMM_W4       mask of the forms the four-wave persistent kernel (gemm256w_kernel) serves (see devias_gemm;
                        //                                        15 = all four; -1, default: the measured policy -- none since round 6, all four where K >= 1024 and N >= 1024 before)
     int splitk_xcd;    // "gemm_splitk_xcd" DEVIAS_GEMM_SPLITK_XCD 1 (default): split-K launches of the 256 x 256 kernel (the weight gradients) order their (slab, tile) pairs XCD-major; 0: (tile, slab) grid

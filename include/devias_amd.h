@@ -236,6 +236,8 @@ int devias_add(const void* a, const void* b, void* y, int32_t dtype, int64_t n, 
  * agg_block/agg_block.py:105-107 eps 1e-5).  x,y: T [M,D]; gamma,beta fp32 [D]; mean,rstd fp32 [M] (saved for backward).
  * backward: dx = LN'(dy) (+ dres if dres != NULL, fusing the residual-branch gradient add);
  *           dgamma/dbeta (fp32 [D]) = beta_acc * old + column sums; ws >= devias_layernorm_bwd_workspace_bytes.
+ *           The backward's partition follows the CUs the library may count on (option gemm_reserve_cus), and so does the workspace
+ *           size: query devias_layernorm_bwd_workspace_bytes again after changing that option; a size queried before is not valid.
  *           dx_colsum (optional fp32 [D]) = column sums of the stored dx: the bias gradient of the Linear layer that produced x's
  *           residual branch input (proj / fc2 bias), obtained for free from the rows this kernel already holds.
  * ------------------------------------------------------------------------------------------------- */

@@ -176,6 +176,49 @@ def test_layernorm(dtype, M, D, eps):
     assert rel(cs, xr.grad.sum(0)) < (1e-4 if dtype == torch.float32 else 2e-2)        # fused bias-gradient column sums of dx
 
 
+@pytest.mark.parametrize("reserve", [0, 8, 16, 64, 200])
+@pytest.mark.parametrize("dtype,M,D", [(torch.bfloat16, 50176, 768), (torch.float32, 20011, 768), (torch.bfloat16, 9001, 1024)])
+def test_layernorm_bwd_workspace_under_reserved_cus(reserve, dtype, M, D):
+    """option gemm_reserve_cus sets the LayerNorm backward's partition (one part per CU it may count on): through the C ABI, with EXACTLY
+    devias_layernorm_bwd_workspace_bytes as queried at that reserve followed by a sentinel region, which must stay untouched; results
+    against fp32 torch at test_layernorm's tolerances."""
+    import ctypes
+    from devias_amd import _lib
+    o = ops()
+    lib = _lib.load()
+    saved = o.get_option("gemm_reserve_cus")
+    try:
+        o.set_option("gemm_reserve_cus", reserve)
+        x = rnd(M, D, dtype=dtype, seed=20) * 2 + 0.5
+        g, b = 1 + 0.1 * rnd(D, seed=21), 0.1 * rnd(D, seed=22)
+        y, mean, rstd = o.layernorm_fwd(x, g, b, 1e-6)
+        dy = rnd(M, D, dtype=dtype, seed=23)
+        nbytes = int(lib.devias_layernorm_bwd_workspace_bytes(M, D))
+        assert nbytes > 0 and nbytes % 16 == 0
+        n, guard = nbytes // 4, 1 << 16
+        buf = torch.empty(n + guard, dtype=torch.float32, device=DEV)
+        buf[n:].fill_(-1234.5)
+        dx = torch.empty_like(x)
+        dg = torch.empty(D, dtype=torch.float32, device=DEV)
+        db = torch.empty(D, dtype=torch.float32, device=DEV)
+        cs = torch.empty(D, dtype=torch.float32, device=DEV)
+        rc = lib.devias_layernorm_bwd(dy.data_ptr(), x.data_ptr(), g.data_ptr(), mean.data_ptr(), rstd.data_ptr(), None, dx.data_ptr(),
+                                      dg.data_ptr(), db.data_ptr(), ctypes.c_float(0.0), cs.data_ptr(), M, D, o.dt_code(dtype), buf.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "devias_layernorm_bwd")
+        torch.cuda.synchronize()
+        assert bool((buf[n:] == -1234.5).all()), f"workspace overrun at reserve {reserve}: {nbytes} bytes queried"
+        xr = x.float().clone().requires_grad_(True)
+        gr, br = g.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        F.layer_norm(xr, (D,), gr, br, 1e-6).backward(dy.float())
+        assert rel(dx.float(), xr.grad) < TOL[dtype]
+        assert rel(dg, gr.grad) < (1e-4 if dtype == torch.float32 else 1e-3)
+        assert rel(db, br.grad) < (1e-4 if dtype == torch.float32 else 1e-3)
+        assert rel(cs, xr.grad.sum(0)) < (1e-4 if dtype == torch.float32 else 2e-2)
+    finally:
+        o.set_option("gemm_reserve_cus", saved)
+
+
 # ---------------------------------------------------------------------------------------------- attention
 def _attn_ref(qkv, B, N, H, scale):
     q, k, v = qkv.float().reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import golden_util as gu
+import grad_compare as gc
 from devias_amd import synth
 from oracle import ref_cpu
 
@@ -18,6 +19,19 @@ pytestmark = pytest.mark.gpu
 TOL_BF16_LOGITS = 1.5e-2
 TOL_BF16_LOSS = 5e-4
 TOL_BF16_GRADNORM_MEDIAN = 2e-3
+# element-wise gradient bounds per family (tests/grad_compare.py: worst of relative Frobenius error and worst 64-row block) of the bf16 step at
+# B = 8 / 16 against the CPU oracle run chunk by chunk, ~2x the worst of the two measured on MI355X (next to each bound).  agg_block's worst is a
+# mathematically zero gradient (the slot-query LayerNorm bias); head (> 5e-2): sums over only B x 2 slot rows, a few 64-row blocks of the mask predictor
+TOL_BF16_GRAD_CHUNKS = {"latents": 1.6e-2,      # 7.7e-3
+                        "patch_embed": 2.4e-2,  # 1.18e-2
+                        "qkv_weight": 2e-2,     # 9.4e-3
+                        "qv_bias": 3.3e-2,      # 1.64e-2
+                        "proj": 1.8e-2,         # 8.9e-3
+                        "fc1": 2.4e-2,          # 1.16e-2
+                        "fc2": 1.8e-2,          # 8.7e-3
+                        "norm": 2.4e-2,         # 1.20e-2
+                        "agg_block": 4.7e-2,    # 2.32e-2
+                        "head": 4e-1}           # 1.95e-1
 
 
 def _build(cfg, dtype, **kw):
@@ -107,6 +121,9 @@ def test_bf16_step_on_full_tile_kernels_vs_reference_chunks(name, B):
     assert max(e_logits) < TOL_BF16_LOGITS
     assert e_total < TOL_BF16_LOSS
     assert np.median(e_gn) < TOL_BF16_GRADNORM_MEDIAN and np.quantile(e_gn, 0.9) < 2e-2
+    # element-wise, not just norms: the oracle's full gradients are at hand
+    gc.check({n: p.grad for n, p in model.named_parameters()}, {n: o_grads[n] / (B // 2) for n in names}, TOL_BF16_GRAD_CHUNKS,
+             f"{name} B={B} bf16 vs oracle chunks")
 
 
 def test_bf16_full_size_step_properties():
