@@ -1,6 +1,10 @@
 // Slot selection + TrainLoss ('matching', scene criterion KL or CE) for gfx950: one workgroup per sample, everything on
 // the device (the reference does B SciPy calls on the host plus six .item() syncs per step,
 // utils/loss/train_loss.py:112-122,183-187).  All statistics in fp32; reductions are wave shuffles + a 4-wave LDS combine.
+// The loss kernels have a compile-time LABELS mode for ground-truth scene labels (utils/loss/hvu_train_loss.py:27-128, the HVU recipe): the scene class is
+// nb + scene_target[b] instead of the teacher's argmax, so there is no teacher_stats (batch minimum, argmax, logsumexp) and no KL loop over C.  There 'CE' (:94)
+// and 'KL' against the one-hot target on a [1, C] input (:96-101: 'batchmean' divides by 1, 0 log 0 = 0) are the same number, lse_j - z_j[nb + scene_target],
+// and the class has no scene weight.
 #include "common.h"
 
 namespace {
@@ -67,6 +71,9 @@ __device__ __forceinline__ TeacherStats teacher_stats(const float* teacher, int 
     return r;
 }
 
+// Labels are data: a sample whose action label is outside [0, nb) or whose scene label is outside [0, ns) is never indexed with (LABELS mode)
+__device__ __forceinline__ bool labels_ok(int64_t y, int64_t ys, int nb, int ns) { return y >= 0 && y < nb && ys >= 0 && ys < ns; }
+
 // ---- slot selection (modeling_slot.py:395-401) ---------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void slot_select_kernel(const T* __restrict__ Z, int S, int C, int nb, int* __restrict__ idx) {
@@ -90,10 +97,11 @@ __global__ __launch_bounds__(256) void slot_select_kernel(const T* __restrict__ 
 }
 
 // ---- loss forward ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool LABELS>
 __global__ __launch_bounds__(256) void loss_fwd_kernel(devias_loss_dims d, const T* __restrict__ Z, const T* __restrict__ slots,
                                                        const T* __restrict__ maskp, const float* __restrict__ attn,
                                                        const float* __restrict__ teacher, const int64_t* __restrict__ target,
+                                                       const int64_t* __restrict__ scene_target,   // LABELS: int64 [B], and `teacher` is not read
                                                        const float* __restrict__ fg, const float* __restrict__ fgN,
                                                        float* __restrict__ per_sample, int* __restrict__ match,
                                                        T* __restrict__ out_logits) {
@@ -102,9 +110,26 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(devias_loss_dims d, const
     __shared__ float s_lse[LMAXS];
     __shared__ int s_ij[2];
     const int b = blockIdx.x, S = d.S, C = d.C;
-    const int y = (int)target[b];
-    TeacherStats ts = teacher_stats(teacher, d.B, d.ns, d.nb, b, sm, smi);
-    const int st = d.nb + ts.argmax;                                           // train_loss.py:100,107
+    TeacherStats ts;
+    int y, st;
+    if constexpr (LABELS) {
+        const int64_t y64 = target[b], ys64 = scene_target[b];
+        if (!labels_ok(y64, ys64, d.nb, d.ns)) {                               // uniform over the workgroup: NaN terms (so the total is NaN), match (0, min(1, S-1))
+            for (int c = threadIdx.x; c < C; c += 256) out_logits[(int64_t)b * C + c] = Z[(int64_t)b * S * C + c];
+            if (threadIdx.x == 0) {
+                float* o = per_sample + (int64_t)b * 5;
+                o[0] = o[1] = o[2] = o[3] = o[4] = __builtin_nanf("");
+                match[2 * b] = 0; match[2 * b + 1] = (S > 1 ? 1 : 0);
+            }
+            return;
+        }
+        y = (int)y64;
+        st = d.nb + (int)ys64;                                                 // hvu_train_loss.py:45-46,54
+    } else {
+        y = (int)target[b];
+        ts = teacher_stats(teacher, d.B, d.ns, d.nb, b, sm, smi);
+        st = d.nb + ts.argmax;                                                 // train_loss.py:100,107
+    }
     for (int s = 0; s < S; ++s) {
         float mx, lse; row_stats(Z + ((int64_t)b * S + s) * C, C, sm, mx, lse);
         if (threadIdx.x == 0) s_lse[s] = lse;
@@ -131,13 +156,18 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(devias_loss_dims d, const
     // scene_criterion 'KL': KL(T || softmax(Z_j)) with 'batchmean' on a 1-D input => / C, times w_scene (:159-164);
     // 'CE': cross-entropy of slot j* against the teacher's argmax class, NOT weighted (:155-156)
     float kl = 0.f;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float lt = (c < d.nb ? ts.pad : teacher[(int64_t)b * d.ns + c - d.nb]) - ts.lse;
-        float lz = to_f32(zj[c]) - s_lse[js];
-        kl += expf(lt) * (lt - lz);
-        out_logits[(int64_t)b * C + c] = zi[c];
+    if constexpr (LABELS) {
+        for (int c = threadIdx.x; c < C; c += 256) out_logits[(int64_t)b * C + c] = zi[c];
+        kl = s_lse[js] - to_f32(zj[st]);                                       // hvu_train_loss.py:94 and :96-101, for either value of scene_ce
+    } else {
+        for (int c = threadIdx.x; c < C; c += 256) {
+            float lt = (c < d.nb ? ts.pad : teacher[(int64_t)b * d.ns + c - d.nb]) - ts.lse;
+            float lz = to_f32(zj[c]) - s_lse[js];
+            kl += expf(lt) * (lt - lz);
+            out_logits[(int64_t)b * C + c] = zi[c];
+        }
+        kl = d.scene_ce ? s_lse[js] - to_f32(zj[st]) : block_sum(kl, sm) * d.w_scene / (float)C;
     }
-    kl = d.scene_ce ? s_lse[js] - to_f32(zj[st]) : block_sum(kl, sm) * d.w_scene / (float)C;
     // BCE-with-logits on the already-sigmoided prediction (double sigmoid, :146-149)
     float mp = 0.f;
     const T* mrow = maskp + ((int64_t)b * S + is) * d.G;
@@ -189,10 +219,11 @@ __global__ void loss_final_kernel(const float* __restrict__ per_sample, int B, f
 }
 
 // ---- loss backward -----------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool LABELS>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(devias_loss_dims d, const T* __restrict__ Z, const T* __restrict__ slots,
                                                        const T* __restrict__ maskp, const float* __restrict__ attn,
                                                        const float* __restrict__ teacher, const int64_t* __restrict__ target,
+                                                       const int64_t* __restrict__ scene_target,
                                                        const float* __restrict__ fg, const float* __restrict__ fgN,
                                                        const int* __restrict__ match, const float* __restrict__ g_total,
                                                        T* __restrict__ dZ, T* __restrict__ dslots, T* __restrict__ dmaskp,
@@ -201,14 +232,33 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(devias_loss_dims d, const
     __shared__ int smi[4];
     const int b = blockIdx.x, S = d.S, C = d.C;
     const float g = g_total[0] / (float)d.B;
-    const int y = (int)target[b];
     const int is = match[2 * b], js = match[2 * b + 1];
-    TeacherStats ts = teacher_stats(teacher, d.B, d.ns, d.nb, b, sm, smi);
+    TeacherStats ts;
+    int y, st;
+    if constexpr (LABELS) {
+        const int64_t y64 = target[b], ys64 = scene_target[b];
+        // a sample with a label out of range (or a match that is not one of its slots) contributes nothing: zeros, and no read through the label
+        if (!labels_ok(y64, ys64, d.nb, d.ns) || is < 0 || is >= S || js < 0 || js >= S) {
+            for (int s = 0; s < S; ++s) {
+                for (int c = threadIdx.x; c < C; c += 256) dZ[((int64_t)b * S + s) * C + c] = from_f32<T>(0.f);
+                for (int k = threadIdx.x; k < d.G; k += 256) dmaskp[((int64_t)b * S + s) * d.G + k] = from_f32<T>(0.f);
+                for (int k = threadIdx.x; k < d.D; k += 256) dslots[((int64_t)b * S + s) * d.D + k] = from_f32<T>(0.f);
+                for (int j = threadIdx.x; j < d.N; j += 256)
+                    for (int hh = 0; hh < d.nh; ++hh) dattn[(((int64_t)b * d.nh + hh) * S + s) * d.N + j] = 0.f;
+            }
+            return;
+        }
+        y = (int)y64;
+        st = d.nb + (int)ys64;
+    } else {
+        y = (int)target[b];
+        ts = teacher_stats(teacher, d.B, d.ns, d.nb, b, sm, smi);
+        st = d.nb + ts.argmax;
+    }
     float lse_i, lse_j, mx;
     row_stats(Z + ((int64_t)b * S + is) * C, C, sm, mx, lse_i);
     row_stats(Z + ((int64_t)b * S + js) * C, C, sm, mx, lse_j);
     const float wk = d.w_scene / (float)C;
-    const int st = d.nb + ts.argmax;
     for (int s = 0; s < S; ++s) {
         const T* z = Z + ((int64_t)b * S + s) * C;
         T* dz = dZ + ((int64_t)b * S + s) * C;
@@ -216,7 +266,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(devias_loss_dims d, const
             float v = 0.f;
             if (s == is) v += g * (expf(to_f32(z[c]) - lse_i) - (c == y ? 1.f : 0.f));
             if (s == js) {
-                if (d.scene_ce) v += g * (expf(to_f32(z[c]) - lse_j) - (c == st ? 1.f : 0.f));
+                if (LABELS || d.scene_ce) v += g * (expf(to_f32(z[c]) - lse_j) - (c == st ? 1.f : 0.f));
                 else {
                     float lt = (c < d.nb ? ts.pad : teacher[(int64_t)b * d.ns + c - d.nb]) - ts.lse;
                     v += g * wk * (expf(to_f32(z[c]) - lse_j) - expf(lt));
@@ -315,11 +365,11 @@ extern "C" int devias_head_match_loss_fwd(const devias_loss_dims* d, const void*
     DEVIAS_REQUIRE(slots_head && slots && maskp && attn && teacher && target && fg && fgN && out_losses && out_match && out_logits && ws,
                    "devias_head_match_loss_fwd: null pointer");
     if (d->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((loss_fwd_kernel<bf16>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
-                           (const bf16*)maskp, attn, teacher, target, fg, fgN, ws, out_match, (bf16*)out_logits);
+        hipLaunchKernelGGL((loss_fwd_kernel<bf16, false>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
+                           (const bf16*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, ws, out_match, (bf16*)out_logits);
     else
-        hipLaunchKernelGGL((loss_fwd_kernel<float>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
-                           (const float*)maskp, attn, teacher, target, fg, fgN, ws, out_match, (float*)out_logits);
+        hipLaunchKernelGGL((loss_fwd_kernel<float, false>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
+                           (const float*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, ws, out_match, (float*)out_logits);
     DEVIAS_CHECK_LAUNCH("devias_head_match_loss_fwd");
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, ws, d->B, out_losses);
     DEVIAS_CHECK_LAUNCH("devias_head_match_loss_fwd(final)");
@@ -336,13 +386,65 @@ extern "C" int devias_head_match_loss_bwd(const devias_loss_dims* d, const void*
     DEVIAS_REQUIRE(slots_head && slots && maskp && attn && teacher && target && fg && fgN && match && g_total && d_slots_head &&
                    d_slots && d_maskp && d_attn, "devias_head_match_loss_bwd: null pointer");
     if (d->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((loss_bwd_kernel<bf16>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
-                           (const bf16*)maskp, attn, teacher, target, fg, fgN, match, g_total, (bf16*)d_slots_head, (bf16*)d_slots,
+        hipLaunchKernelGGL((loss_bwd_kernel<bf16, false>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
+                           (const bf16*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, match, g_total, (bf16*)d_slots_head, (bf16*)d_slots,
                            (bf16*)d_maskp, d_attn);
     else
-        hipLaunchKernelGGL((loss_bwd_kernel<float>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
-                           (const float*)maskp, attn, teacher, target, fg, fgN, match, g_total, (float*)d_slots_head, (float*)d_slots,
+        hipLaunchKernelGGL((loss_bwd_kernel<float, false>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
+                           (const float*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, match, g_total, (float*)d_slots_head, (float*)d_slots,
                            (float*)d_maskp, d_attn);
     DEVIAS_CHECK_LAUNCH("devias_head_match_loss_bwd");
+    return DEVIAS_OK;
+}
+
+// ---- ground-truth scene labels: the LABELS mode of the two kernels above (devias_amd.h) ----------------------------------------------------
+static int check_label_dims(const devias_loss_dims* d, const char* who) {
+    int rc = check_dims(d, who);
+    if (rc) return rc;
+    if (d->nb <= 0 || d->ns <= 0) return devias_set_error(DEVIAS_EINVAL, "%s: bad dims nb=%d ns=%d (both must be positive)", who, d->nb, d->ns);
+    return DEVIAS_OK;
+}
+
+extern "C" int devias_head_match_loss_labels_fwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
+                                                 const float* attn, const int64_t* target, const int64_t* scene_target, const float* fg,
+                                                 const float* fgN, float* out_losses, int32_t* out_match, void* out_logits, float* ws,
+                                                 void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_label_dims(d, "devias_head_match_loss_labels_fwd");
+    if (rc) return rc;
+    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && target && scene_target && fg && fgN && out_losses && out_match && out_logits && ws,
+                   "devias_head_match_loss_labels_fwd: null pointer");
+    if (d->dtype == DEVIAS_BF16)
+        hipLaunchKernelGGL((loss_fwd_kernel<bf16, true>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
+                           (const bf16*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, ws, out_match, (bf16*)out_logits);
+    else
+        hipLaunchKernelGGL((loss_fwd_kernel<float, true>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
+                           (const float*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, ws, out_match, (float*)out_logits);
+    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_labels_fwd");
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, ws, d->B, out_losses);
+    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_labels_fwd(final)");
+    devias_count(DEVIAS_CNT_LOSS_LABELS);
+    return DEVIAS_OK;
+}
+
+extern "C" int devias_head_match_loss_labels_bwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
+                                                 const float* attn, const int64_t* target, const int64_t* scene_target, const float* fg,
+                                                 const float* fgN, const int32_t* match, const float* g_total, void* d_slots_head,
+                                                 void* d_slots, void* d_maskp, float* d_attn, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_label_dims(d, "devias_head_match_loss_labels_bwd");
+    if (rc) return rc;
+    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && target && scene_target && fg && fgN && match && g_total && d_slots_head &&
+                   d_slots && d_maskp && d_attn, "devias_head_match_loss_labels_bwd: null pointer");
+    if (d->dtype == DEVIAS_BF16)
+        hipLaunchKernelGGL((loss_bwd_kernel<bf16, true>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
+                           (const bf16*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, match, g_total, (bf16*)d_slots_head,
+                           (bf16*)d_slots, (bf16*)d_maskp, d_attn);
+    else
+        hipLaunchKernelGGL((loss_bwd_kernel<float, true>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
+                           (const float*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, match, g_total, (float*)d_slots_head,
+                           (float*)d_slots, (float*)d_maskp, d_attn);
+    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_labels_bwd");
+    devias_count(DEVIAS_CNT_LOSS_LABELS);
     return DEVIAS_OK;
 }

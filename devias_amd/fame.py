@@ -57,7 +57,9 @@ class FAME(nn.Module):
         return binmask.view(B, S, H, W), pooled[:, 0], pooled[:, 1:]
 
     @torch.no_grad()
-    def forward(self, videos, label, center_frame=None, index=None, rand_batch=None):
+    def _mix(self, videos, index=None, rand_batch=None):
+        """masks + the fg/bg mixing launch shared by every forward: returns the mixed clips, the int32 device table [3, B] of
+        (source clip, background partner, augmented?) per output row, and the two pooled masks in output order"""
         B, C, T, H, W = videos.shape
         videos = videos.contiguous()
         binmask, pooled, pooled_pf = self.masks(videos)
@@ -80,9 +82,43 @@ class FAME(nn.Module):
         _call("devias_fame_mix", videos.data_ptr(), binmask.data_ptr(), S * H * W, tab[0].data_ptr(), tab[1].data_ptr(), tab[2].data_ptr(),
               out.data_ptr(), B, C * T, H * W, ops._stream())
         src_d = tab[0].long()
-        all_label = label.to(dev)[src_d]
         mask = pooled[src_d].contiguous().to(videos.dtype)
         masks_per_frame = pooled_pf[src_d].reshape(B, -1).to(videos.dtype)
+        return out, tab, (mask, masks_per_frame)
+
+    @torch.no_grad()
+    def forward(self, videos, label, center_frame=None, index=None, rand_batch=None):
+        out, tab, masks = self._mix(videos, index, rand_batch)
+        dev = out.device
+        src_d = tab[0].long()
+        all_label = label.to(dev)[src_d]
         if center_frame is not None:
-            return out, all_label, (mask, masks_per_frame), center_frame.to(dev)[src_d]
-        return out, all_label, (mask, masks_per_frame)
+            return out, all_label, masks, center_frame.to(dev)[src_d]
+        return out, all_label, masks
+
+
+def route_hvu_labels(action_label, scene_label, src, partner, aug, prob_aug):
+    """Labels of the HVU variant's output rows (utils/transform/fame_hvu.py:126-141), as index arithmetic on whatever device the tensors
+    live on: row r shows clip src[r], with the background of clip partner[r] where aug[r].  The action label is the clip's own; an
+    augmented clip takes the SCENE label of the clip whose background it received (`scene_label[index]`, :127, :135).
+    With prob_aug >= 1 the reference returns the scene labels as they came in although every clip is mixed (:138-141); so does this."""
+    src, partner = src.long(), partner.long()
+    if prob_aug >= 1:
+        return action_label[src], scene_label[src]
+    return action_label[src], torch.where(aug.bool(), scene_label[partner], scene_label[src])
+
+
+class FAMEHVU(FAME):
+    """utils/transform/fame_hvu.py: FAME for clips that carry an action AND a scene label (engine_for_slot_hvu.py:64-65:
+    `samples, action_targets, scene_targets, masks = mask_model(samples, action_targets, scene_targets)`).  Masks and mixing are FAME's;
+    the labels are routed on the device by route_hvu_labels (no host sync).  `repr` contains 'FAME': the engine dispatches on it."""
+
+    def __repr__(self):
+        return "HVU-" + super().__repr__()
+
+    @torch.no_grad()
+    def forward(self, videos, action_label, scene_label, index=None, rand_batch=None):
+        out, tab, masks = self._mix(videos, index, rand_batch)
+        dev = out.device
+        all_action, all_scene = route_hvu_labels(action_label.to(dev), scene_label.to(dev), tab[0], tab[1], tab[2], self.prob_aug)
+        return out, all_action, all_scene, masks

@@ -106,6 +106,12 @@ def targets(batch: int, num_classes: int = 400, seed: int = 1000, first: int = 0
     return torch.from_numpy((h % np.uint64(num_classes)).astype(np.int64))
 
 
+def scene_targets(batch: int, num_scene: int = 248, seed: int = 1000, first: int = 0) -> torch.Tensor:
+    """ground-truth scene labels in [0, num_scene) (the HVU recipe; 248 = run_slot_finetuning_hvu.py:36), hashed like `targets` on their own key"""
+    h = np.array([hash_u64(seed, f"scene_target.{first + b}", 1)[0] for b in range(batch)], dtype=np.uint64)
+    return torch.from_numpy((h % np.uint64(num_scene)).astype(np.int64))
+
+
 def teacher_logits(batch: int, num_scene: int = 365, seed: int = 1000, first: int = 0) -> torch.Tensor:
     out = np.empty((batch, num_scene), dtype=np.float32)
     for b in range(batch):

@@ -73,6 +73,7 @@ const char* devias_last_error(void);
 #define DEVIAS_CNT_DKDV1W_REST 17    /* its second launch for the N mod 256 last keys of every head (32 keys at N = 1568) */
 #define DEVIAS_CNT_DKDV2W 18         /* the two-waves-per-SIMD kernel of rounds 2-4 (attention dropout, ws = NULL, option attn_dkdv = 0) */
 #define DEVIAS_CNT_MHSA_QPRE 19      /* bf16 attention calls (forward or backward) served with DEVIAS_ATTN_Q_PRESCALED (ABI 167): 2 per encoder block and step in the measured path */
+#define DEVIAS_CNT_LOSS_LABELS 20    /* devias_head_match_loss_labels_fwd / _bwd calls (ABI 168): 2 per step whose loss was served by the ground-truth-label kernels */
 #define DEVIAS_CNT_MAX 24
 int64_t devias_counter(int32_t id);          /* -1 for an unknown id */
 void devias_counters_reset(void);
@@ -384,6 +385,29 @@ int devias_head_match_loss_bwd(const devias_loss_dims* d, const void* slots_head
                                const float* fgN, const int32_t* match, const float* g_total,
                                void* d_slots_head, void* d_slots, void* d_maskp, float* d_attn, void* stream);
 int64_t devias_head_match_loss_workspace_bytes(int32_t B);
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 168: the same loss with GROUND-TRUTH scene labels instead of a scene teacher -- the HVU recipe's TrainLoss
+ * (utils/loss/hvu_train_loss.py:27-128; also a host that cached the teacher's argmax offline).  Same tensor contracts, output layout
+ * (out_losses[6], out_match[B,2], out_logits[B,C]) and workspace query (devias_head_match_loss_workspace_bytes) as above, with
+ *   target int64 [B] in [0, nb); scene_target int64 [B] in [0, ns), NOT offset by nb; d->ns = number of scene classes, C == nb + ns, nb > 0, ns > 0.
+ * The scene column of the S x 2 assignment is nb + scene_target[b] (:45-54).  d->w_scene is ignored (that class has no scene weight).
+ * d->scene_ce may be 0 or 1 and both give the SAME scene term, lse_j - z_j[nb + scene_target]: 'CE' is cross_entropy (:94); 'KL' is
+ * kl_div(log_softmax(z)[None], one_hot, 'batchmean') on a [1, C] input (:96-101), which divides by 1 and with 0 log 0 = 0 is that number.
+ * Backward of the scene slot: g (softmax(z_j) - onehot(nb + scene_target)).  No batch-wide statistic is read: a sample's result depends on that sample only.
+ * Labels are data: where target[b] is outside [0, nb) or scene_target[b] outside [0, ns), nothing is read through that index; the forward writes
+ * NaN to that sample's five terms (so out_losses is NaN in every entry: hosts stop on a non-finite loss), match (0, min(1, S-1)) and
+ * out_logits[b] = slots_head[b, 0]; the backward writes zeros to that sample's rows of all four gradients.
+ * Both calls count DEVIAS_CNT_LOSS_LABELS.
+ * ------------------------------------------------------------------------------------------------- */
+int devias_head_match_loss_labels_fwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
+                                      const float* attn, const int64_t* target, const int64_t* scene_target, const float* fg,
+                                      const float* fgN, float* out_losses, int32_t* out_match, void* out_logits,
+                                      float* ws, void* stream);
+int devias_head_match_loss_labels_bwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
+                                      const float* attn, const int64_t* target, const int64_t* scene_target, const float* fg,
+                                      const float* fgN, const int32_t* match, const float* g_total,
+                                      void* d_slots_head, void* d_slots, void* d_maskp, float* d_attn, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Fused AdamW over a flat fp32 parameter range (torch.optim.AdamW semantics, utils/optim_factory.py:132-133;
