@@ -17,6 +17,8 @@ from typing import Optional
 
 import torch
 
+from .weight_cache import invalidate_weight_cache
+
 
 def select_model_state(checkpoint: dict, model_key: str = "model|module") -> dict:
     for k in model_key.split("|"):
@@ -75,7 +77,6 @@ def load_state_dict(model: torch.nn.Module, state_dict: dict, prefix: str = "", 
                 load(child, pfx + name + ".")
 
     load(model, prefix)
-    from .modeling_slot import invalidate_weight_cache
     invalidate_weight_cache()          # belt and braces: copy_ under no_grad already moves Tensor._version
     warn = [k for k in missing if not any(ig in k for ig in ignore_missing.split("|"))]
     if warn:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .weight_cache import invalidate_weight_cache
 
 _REC = np.dtype([("param", "<u8"), ("grad", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("lr", "<f4"), ("wd", "<f4"),
                  ("bc1", "<f4"), ("bc2s", "<f4"), ("reserved", "<i8")])
@@ -98,7 +99,6 @@ class FusedAdamW(torch.optim.Optimizer):
         if by_hyper:
             # the kernels below write parameters through raw pointers (Tensor._version does not move): compute-dtype weight copies
             # held by the model code are stale from here on (stale bf16 weights after the first step)
-            from .modeling_slot import invalidate_weight_cache
             invalidate_weight_cache()
         if not self.multi_tensor:
             if max_norm is not None:

@@ -5,7 +5,7 @@ Replaces DDP / DeepSpeed ZeRO-0 gradient all-reduce of the reference (run_slot_f
   * parameters are bucketed in REVERSE registration order (head / mask_predictor / agg_block first, then blocks.11 ... 0,
     patch_embed last) -- the order backward produces their gradients;
   * every parameter gets the fp32 view of its place in the flat bucket (`p._devias_grad_out`): the weight-gradient kernels of the
-    encoder blocks write straight into it (modeling_slot._gout), autograd adopts the view as `.grad`, and nothing is packed;
+    encoder blocks write straight into it (functions._gout), autograd adopts the view as `.grad`, and nothing is packed;
     gradients that arrive as other tensors (small agg-block / head ones) are copied into their view by the hook;
   * when the last gradient of a bucket has arrived (post-accumulate-grad hook) an event is recorded on the compute stream and the
     all-reduce is enqueued on the side stream;
@@ -24,6 +24,8 @@ from typing import List, Optional
 
 import torch
 import torch.distributed as dist
+
+from .weight_cache import invalidate_weight_cache
 
 
 def _os_environ_flag(name: str) -> bool:
@@ -92,7 +94,7 @@ class GradSync:
                 v = flat[off:off + p.numel()].view(p.shape)
                 self._view[p] = v
                 self._where[p] = bi
-                p._devias_grad_out = v                 # destination of the weight-gradient kernels (modeling_slot._gout)
+                p._devias_grad_out = v                 # destination of the weight-gradient kernels (functions._gout)
                 off += _al(p.numel())
         self._comm = [None] * len(self.buckets)        # bf16 wire buffers (comm_dtype = bf16 only)
         self._pending = [0] * len(self.buckets)
@@ -275,5 +277,4 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0, process_group=No
         return
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src=src, group=process_group)
-    from .modeling_slot import invalidate_weight_cache
     invalidate_weight_cache()              # `.data` writes do not move Tensor._version

@@ -1,0 +1,283 @@
+"""The fused regions: ONE library call per region and direction (devias_encoder_block_* / devias_agg_block_* / devias_head_*).
+
+The kernel sequence of a region is issued by the library (csrc/regions.hip) -- the same launches in the same order as the per-kernel
+Functions of devias_amd.functions, bitwise the same results (tests/test_regions_gpu.py) -- so a step costs ~40 Python -> library hops instead of ~750.
+What backward needs lives in ONE arena tensor per region call, backward temporaries in a grow-only scratch buffer per stream, the
+parameter gradients of a region in one flat fp32 tensor (or straight in the data-parallel gradient bucket views).
+"""
+from __future__ import annotations
+
+import ctypes as _ct
+import math
+
+import torch
+from torch.autograd import Function
+
+from . import _lib as _L
+from . import ops
+from .functions import _LAYER_KEYS, _gout, _peek_colsum, _publish_colsum, _weight_sets
+from .weight_cache import _Q_PRESCALE, _WCACHE, _f32, _use_q_prescale
+
+_scratch_bufs = {}
+
+
+def _scratch(nbytes: int, device) -> torch.Tensor:
+    """grow-only backward scratch per (device, stream): the temporaries of a region's backward are dead when its kernels have run, and the
+    kernels of one stream are ordered"""
+    key = (torch.device(device).index or 0, torch.cuda.current_stream(device).cuda_stream)
+    buf = _scratch_bufs.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = None
+        _scratch_bufs.pop(key, None)
+        buf = _scratch_bufs[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return buf
+
+
+class _GradDest:
+    """fp32 gradient destinations of one region: a parameter whose gradient bucket view is free gets that view (a fresh alias, see _gout);
+    the others are carved out of ONE flat tensor"""
+
+    def __init__(self, items, device):
+        self.out = []
+        views = [(_gout(p, shape) if p is not None else None) for p, shape in items]
+        total = 0
+        for (p, shape), v in zip(items, views):
+            if v is None:
+                total += (math.prod(shape) + 63) // 64 * 64           # 256-byte aligned pieces
+        flat = torch.empty((total,), dtype=torch.float32, device=device) if total else None
+        off = 0
+        for (p, shape), v in zip(items, views):
+            if v is None:
+                n = math.prod(shape)
+                v = flat[off:off + n].view(shape)
+                off += (n + 63) // 64 * 64
+            self.out.append(v)
+
+    def ptrs(self):
+        return [t.data_ptr() for t in self.out]
+
+
+def _region_state(ctx, who: str, x: torch.Tensor):
+    """The fused-region Functions keep their arena, weight copies and argument struct on `ctx` as raw pointers (not save_for_backward: the arena is
+    written by the library, not by autograd) and drop them after ONE backward.  A second backward (retain_graph=True) or an input modified in place
+    between forward and backward must fail with a message, not with a TypeError on None or silently wrong gradients."""
+    if ctx.keep is None:
+        raise RuntimeError(f"{who}: backward already consumed this region's saved arena; the fused regions support ONE backward per forward "
+                           "(run forward again instead of retain_graph=True)")
+    if x._version != ctx.x_version:
+        raise RuntimeError(f"{who}: the region's input was modified in place between forward and backward (version {ctx.x_version} -> {x._version}); "
+                           "its saved activations no longer match it")
+
+
+class EncoderBlockRegionFn(Function):
+    """EncoderBlockFn as one devias_encoder_block_fwd / _bwd call (Block.forward, modeling_slot.py:142-152)"""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, qkvw, qb, vb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, meta, ds1=None, ds2=None):
+        B, N, H, eps, cdt = meta
+        lib = _L.load()
+        dev = x.device
+        D = x.shape[1]
+        hid = f1w.shape[0]
+        dt = ops.dt_code(cdt)
+        x = x.contiguous()
+        keep = [_f32(n1w), _f32(n1b), _f32(n2w), _f32(n2b)] + [_WCACHE.get(w, cdt) for w in (qkvw, pw, f1w, f2w)] + \
+               [_WCACHE.qkv_bias(qb, vb), _f32(pb), _f32(f1b), _f32(f2b)]
+        save = torch.empty((lib.devias_encoder_block_save_bytes(B, N, D, H, hid, dt),), dtype=torch.uint8, device=dev)
+        ws = ops.workspace(lib.devias_encoder_block_workspace_bytes(B, N, D, H, hid, dt), dev)
+        a = _L.BlockArgs()
+        a.B, a.N, a.D, a.H, a.hidden, a.dtype, a.eps = B, N, D, H, hid, dt, eps
+        (a.n1w, a.n1b, a.n2w, a.n2b, a.Wqkv, a.Wp, a.W1, a.W2, a.qkv_bias, a.pb, a.b1, a.b2) = [t.data_ptr() for t in keep]
+        if _use_q_prescale(cdt):
+            qs = [_WCACHE.get_qscaled(qkvw, D, _Q_PRESCALE, cdt), _WCACHE.get_qscaled(keep[8], D, _Q_PRESCALE, torch.float32)]
+            keep = keep + qs
+            a.WqkvS, a.qkv_biasS = qs[0].data_ptr(), qs[1].data_ptr()
+        if cdt != torch.float32 and any(ctx.needs_input_grad):
+            # transposed weight copies for the four dgrad GEMMs of the backward (bf16 mode: the fp32 parity kernels stage through registers and do not care)
+            wt = [_WCACHE.get_t(w, cdt) for w in (qkvw, pw, f1w, f2w)]
+            keep = keep + wt
+            (a.WqkvT, a.WpT, a.W1T, a.W2T) = [t.data_ptr() for t in wt]
+        a.ds1 = ds1.data_ptr() if ds1 is not None else None
+        a.ds2 = ds2.data_ptr() if ds2 is not None else None
+        a.save, a.ws, a.ws_bytes = save.data_ptr(), ws.data_ptr(), ws.numel() * 4
+        x2 = torch.empty_like(x)
+        _L.check(lib.devias_encoder_block_fwd(_ct.byref(a), x.data_ptr(), x2.data_ptr(), ops._stream()), "devias_encoder_block_fwd")
+        ctx.args = a
+        ctx.meta = meta
+        ctx.keep = (keep, save, ds1, ds2, x)
+        ctx.x_version = x._version
+        ctx.params = (n1w, n1b, qkvw, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, qb, vb)
+        return x2
+
+    @staticmethod
+    def backward(ctx, dx2):
+        B, N, H, eps, cdt = ctx.meta
+        lib = _L.load()
+        _region_state(ctx, "EncoderBlockRegionFn", ctx.keep[4] if ctx.keep is not None else None)
+        a = ctx.args
+        keep, save, ds1, ds2, x = ctx.keep
+        (p_n1w, p_n1b, p_qkvw, p_pw, p_pb, p_n2w, p_n2b, p_f1w, p_f1b, p_f2w, p_f2b, p_qb, p_vb) = ctx.params
+        dev = x.device
+        D, hid = a.D, a.hidden
+        dx2 = dx2.contiguous()
+        ready = _peek_colsum(dx2) if ds2 is None else None          # colsum(dx2) = fc2 bias gradient, published by the next block's LayerNorm backward
+        b2_dst = _gout(p_f2b) if ready is not None else None
+        # (q_bias and v_bias are two parameters: their gradients go to two destinations -- bucket views under GradSync, else pieces of the flat tensor --
+        # instead of one [3D] vector that autograd would have to slice and GradSync to copy: 24 device-to-device copies per step, +1.0 ms)
+        gd = _GradDest([(p_n1w, (D,)), (p_n1b, (D,)), (p_qkvw, (3 * D, D)), (p_qb, (D,)), (p_pw, (D, D)), (p_pb, (D,)), (p_n2w, (D,)), (p_n2b, (D,)),
+                        (p_f1w, (hid, D)), (p_f1b, (hid,)), (p_f2w, (D, hid)), (None if ready is not None else p_f2b, (1,) if ready is not None else (D,)),
+                        (None, (D,)), (p_vb, (D,))], dev)
+        g = _L.BlockGrads()
+        (g.dn1w, g.dn1b, g.dWqkv, g.dbq, g.dWp, g.dbp, g.dn2w, g.dn2b, g.dW1, g.db1, g.dW2, g.db2, g.dx_colsum, g.dbv) = gd.ptrs()
+        g.db2_done = 1 if ready is not None else 0
+        ws = ops.workspace(a.ws_bytes, dev)                 # (the stream's workspace may have been re-allocated larger since forward)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        nscr = lib.devias_encoder_block_scratch_bytes(B, N, D, H, hid, a.dtype)
+        scr = _scratch(nscr, dev)
+        dx = torch.empty_like(x)
+        _L.check(lib.devias_encoder_block_bwd(_ct.byref(a), x.data_ptr(), dx2.data_ptr(), dx.data_ptr(), _ct.byref(g), scr.data_ptr(), scr.numel(), ops._stream()),
+                 "devias_encoder_block_bwd")
+        ctx.keep = ctx.args = None
+        (dn1w, dn1b, dWqkv, dbq, dWp, dbp, dn2w, dn2b, dW1, db1, dW2, db2, dxs, dbv) = gd.out
+        if ready is not None:
+            db2 = ready if b2_dst is None else b2_dst.copy_(ready)
+        _publish_colsum(dx, dxs)
+        return (dx, dn1w, dn1b, dWqkv, dbq, dbv, dWp, dbp, dn2w, dn2b, dW1, db1, dW2, db2, None, None, None)
+
+
+class HeadRegionFn(Function):
+    """HeadFn as one devias_head_fwd / _bwd call"""
+
+    @staticmethod
+    def forward(ctx, slots, hw, hb, w0, b0, w2, b2, w4, b4, cdt, drop_mask=None):
+        lib = _L.load()
+        dev = slots.device
+        slots = slots.contiguous()
+        R, D = slots.shape
+        C, h1, h2, G = hw.shape[0], w0.shape[0], w2.shape[0], w4.shape[0]
+        dt = ops.dt_code(cdt)
+        keep = [_WCACHE.get(w, cdt) for w in (hw, w0, w2, w4)] + [_f32(hb), _f32(b0), _f32(b2), _f32(b4)]
+        ws = ops.workspace(lib.devias_head_workspace_bytes(R, D, C, h1, h2, G, dt), dev)
+        a = _L.HeadArgs()
+        a.R, a.D, a.C, a.h1, a.h2, a.G, a.dtype = R, D, C, h1, h2, G, dt
+        (a.Wh, a.W0, a.W2, a.W4, a.bh, a.b0, a.b2, a.b4) = [t.data_ptr() for t in keep]
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        if drop_mask is not None:            # fc_dropout (modeling_slot.py:291,393): 0 / (1/keep) per element of the head's input
+            drop_mask = ops._chk(drop_mask, "head.drop_mask", torch.float32)
+            assert drop_mask.shape == (R, D)
+            a.drop_mask = drop_mask.data_ptr()
+        save = torch.empty((lib.devias_head_save_bytes(R, D, h1, h2, dt),), dtype=torch.uint8, device=dev)
+        Z = torch.empty((R, C), dtype=cdt, device=dev)
+        Mk = torch.empty((R, G), dtype=cdt, device=dev)
+        _L.check(lib.devias_head_fwd(_ct.byref(a), slots.data_ptr(), Z.data_ptr(), Mk.data_ptr(), save.data_ptr(), ops._stream()), "devias_head_fwd")
+        ctx.args = a
+        ctx.keep = (keep, save, slots, Mk, drop_mask)
+        ctx.x_version = slots._version
+        ctx.params = (hw, hb, w0, b0, w2, b2, w4, b4)
+        return Z, Mk
+
+    @staticmethod
+    def backward(ctx, dZ, dM):
+        lib = _L.load()
+        _region_state(ctx, "HeadRegionFn", ctx.keep[2] if ctx.keep is not None else None)
+        a = ctx.args
+        keep, save, slots, Mk, drop_mask = ctx.keep
+        hw, hb, w0, b0, w2, b2, w4, b4 = ctx.params
+        dev = slots.device
+        dZ = dZ.contiguous() if dZ is not None else torch.zeros((a.R, a.C), dtype=slots.dtype, device=dev)
+        dM = dM.contiguous() if dM is not None else torch.zeros_like(Mk)
+        gd = _GradDest([(hw, tuple(hw.shape)), (hb, tuple(hb.shape)), (w0, tuple(w0.shape)), (b0, tuple(b0.shape)), (w2, tuple(w2.shape)), (b2, tuple(b2.shape)),
+                        (w4, tuple(w4.shape)), (b4, tuple(b4.shape))], dev)
+        g = _L.HeadGrads()
+        (g.dWh, g.dbh, g.dW0, g.db0, g.dW2, g.db2, g.dW4, g.db4) = gd.ptrs()
+        ws = ops.workspace(a.ws_bytes, dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        dslots = torch.empty_like(slots)
+        _L.check(lib.devias_head_bwd(_ct.byref(a), slots.data_ptr(), Mk.data_ptr(), save.data_ptr(), dZ.data_ptr(), dM.data_ptr(), dslots.data_ptr(),
+                                     _ct.byref(g), ops._stream()), "devias_head_bwd")
+        ctx.keep = ctx.args = None
+        return (dslots, *gd.out, None, None)
+
+
+_AGG_MATS = ("to_q", "to_k", "to_v", "to_out_w", "ff0_w", "ff3_w")                       # -> devias_agg_layer_params.Wq Wk Wv Wo W1 W2
+_AGG_VECS = ("to_out_b", "norm_w", "norm_b", "ctx_w", "ctx_b", "ff0_b", "ff3_b", "ffn_w", "ffn_b")   # -> bo norm_w norm_b ctx_w ctx_b b1 b2 ffn_w ffn_b
+# (devias_agg_layer_grads -- dWq dWk dWv dWo dbo dnorm_w dnorm_b dctx_w dctx_b dW1 db1 dW2 db2 dffn_w dffn_b -- is in _LAYER_KEYS order)
+
+
+class AggBlockRegionFn(Function):
+    """AggBlockFoldFn as one devias_agg_block_fwd / _bwd call"""
+
+    @staticmethod
+    def forward(ctx, x, norm_w, norm_b, latents, last_w, last_b, meta, *layer_params):
+        B, N, S, depth, tied, heads, dh, eps_enc, eps_agg, cdt = meta
+        lib = _L.load()
+        dev = x.device
+        x = x.contiguous()
+        D = x.shape[1]
+        nset = 1 if tied else depth
+        assert depth <= _L.AGG_MAX_DEPTH
+        LP = _weight_sets(layer_params, nset)
+        dt = ops.dt_code(cdt)
+        a = _L.AggArgs()
+        a.B, a.N, a.S, a.D, a.depth, a.tied, a.heads, a.dh, a.ff, a.dtype = B, N, S, D, depth, int(bool(tied)), heads, dh, LP[0]["ff0_w"].shape[0], dt
+        a.eps_enc, a.eps_agg = eps_enc, eps_agg
+        keep = [_f32(norm_w), _f32(norm_b), _f32(latents), _f32(last_w), _f32(last_b)]
+        (a.norm_w, a.norm_b, a.latents, a.last_w, a.last_b) = [t.data_ptr() for t in keep]
+        for i, P in enumerate(LP):
+            mats = [_WCACHE.get(P[k], cdt) for k in _AGG_MATS]
+            vecs = [_f32(P[k]) for k in _AGG_VECS]
+            keep += mats + vecs
+            for f, t in zip(_L.AGG_PARAM_FIELDS, mats + vecs):
+                setattr(a.sets[i], f, t.data_ptr())
+        save = torch.empty((lib.devias_agg_block_save_bytes(_ct.byref(a)),), dtype=torch.uint8, device=dev)
+        a.save = save.data_ptr()
+        ws = ops.workspace(lib.devias_agg_block_workspace_bytes(_ct.byref(a)), dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        slots = torch.empty((B * S, D), dtype=cdt, device=dev)
+        attn_ptr = _ct.c_void_p()
+        _L.check(lib.devias_agg_block_fwd(_ct.byref(a), x.data_ptr(), slots.data_ptr(), _ct.byref(attn_ptr), ops._stream()), "devias_agg_block_fwd")
+        off = attn_ptr.value - save.data_ptr()
+        # the last layer's slot softmax is a VIEW of the arena (no copy of 2.4 MB per step): whoever keeps `attn` alive keeps the whole arena alive,
+        # and it is overwritten by nothing (an arena belongs to one forward); clone it to hold it beyond the step
+        attn = save[off:off + B * heads * S * N * 4].view(torch.float32).view(B * heads, S, N)
+        ctx.args = a
+        ctx.meta = meta
+        ctx.keep = (keep, save, x)
+        ctx.x_version = x._version
+        ctx.params = (norm_w, norm_b, latents, last_w, last_b, LP)
+        return slots, attn
+
+    @staticmethod
+    def backward(ctx, dslots, dattn):
+        B, N, S, depth, tied, heads, dh, eps_enc, eps_agg, cdt = ctx.meta
+        lib = _L.load()
+        _region_state(ctx, "AggBlockRegionFn", ctx.keep[2] if ctx.keep is not None else None)
+        a = ctx.args
+        keep, save, x = ctx.keep
+        norm_w, norm_b, latents, last_w, last_b, LP = ctx.params
+        dev = x.device
+        D = a.D
+        nset = 1 if tied else depth
+        items = [(norm_w, (D,)), (norm_b, (D,)), (latents, tuple(latents.shape)), (last_w, (D,)), (last_b, (D,)), (None, (D,))]
+        for P in LP:
+            items += [(P[k], tuple(P[k].shape)) for k in _LAYER_KEYS]
+        gd = _GradDest(items, dev)
+        ptrs = gd.ptrs()
+        g = _L.AggGrads()
+        (g.dnorm_w, g.dnorm_b, g.dlatents, g.dlast_w, g.dlast_b, g.dx_colsum) = ptrs[:6]
+        nk = len(_LAYER_KEYS)
+        for i in range(nset):
+            for f, ptr in zip(_L.AGG_GRAD_FIELDS, ptrs[6 + nk * i:6 + nk * (i + 1)]):
+                setattr(g.sets[i], f, ptr)
+        ws = ops.workspace(a.ws_bytes, dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        scr = _scratch(lib.devias_agg_block_scratch_bytes(_ct.byref(a)), dev)
+        dslots = dslots.contiguous()
+        dattn = dattn.contiguous() if dattn is not None else None
+        dx = torch.empty_like(x)
+        _L.check(lib.devias_agg_block_bwd(_ct.byref(a), x.data_ptr(), dslots.data_ptr(), dattn.data_ptr() if dattn is not None else None, dx.data_ptr(),
+                                          _ct.byref(g), scr.data_ptr(), scr.numel(), ops._stream()), "devias_agg_block_bwd")
+        ctx.keep = ctx.args = None
+        out = gd.out
+        _publish_colsum(dx, out[5])
+        return (dx, out[0], out[1], out[2], out[3], out[4], None, *out[6:])

@@ -254,7 +254,7 @@ def test_weight_copies_follow_the_optimizer_step():
     updated values (every cached copy -- bf16, transposed, q-scaled, qkv bias -- made anew): loss, outputs and every gradient bitwise equal.
     A copy the update failed to refresh (a transposed weight read only by the backward's dgrad GEMMs, the q-scaled qkv weight) breaks the equality.
     M = 8 x 1568 = 49 x 256 rows: the 256^2 kernels serve the encoder GEMMs."""
-    from devias_amd.modeling_slot import _WCACHE
+    from devias_amd.weight_cache import _WCACHE
     from devias_amd.optim import FusedAdamW
     cfg = ref_cpu.SlotViTConfig(all_frames=16, depth=4)
     data = _data(cfg, 8)

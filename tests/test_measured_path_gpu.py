@@ -365,7 +365,7 @@ def test_bf16_weights_follow_the_fused_optimizer():
     """FusedAdamW updates parameters through raw pointers, which does not move Tensor._version -- the cached bf16
     weight copies must be refreshed anyway.  With every bias / LayerNorm / latent frozen, the logits can only change through the
     bf16 MATRIX copies: they must change after opt.step(), by what the fp32 parity mode (no copies) says they change."""
-    from devias_amd.modeling_slot import _WCACHE
+    from devias_amd.weight_cache import _WCACHE
     from devias_amd.optim import FusedAdamW
     cfg = ref_cpu.SlotViTConfig(embed_dim=384, num_heads=6, depth=2, all_frames=2, agg_depth=2)
     B = 2
@@ -404,7 +404,7 @@ def test_colsum_handoff_and_gradient_destinations():
     """(i) the bias-gradient column sums ride on the gradient tensors between backward regions (no address-keyed global):
     every encoder block but the last consumer must hit; (ii) with a GradSync attached (world 1), the encoder weight gradients are
     written straight into the flat buckets (p.grad IS the bucket view, nothing packed) and equal the gradients without GradSync bitwise."""
-    from devias_amd import modeling_slot as ms
+    from devias_amd import functions as ms
     from devias_amd.parallel import GradSync
     cfg = ref_cpu.SlotViTConfig(embed_dim=384, num_heads=6, depth=3, all_frames=2, agg_depth=2)
     B = 2

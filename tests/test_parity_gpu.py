@@ -192,7 +192,8 @@ def test_train_class_batch_with_teacher_and_fused_adamw():
 def test_drop_path_matches_oracle_with_the_same_masks():
     """stochastic depth (timm drop_path): with the SAME per-sample masks the fused row-scale epilogue path must equal the oracle
     block evaluated with those masks, forward and backward (fp32)"""
-    from devias_amd.modeling_slot import EncoderBlockFn, _f32
+    from devias_amd.functions import EncoderBlockFn
+    from devias_amd.weight_cache import _f32
     cfg = ref_cpu.SlotViTConfig(all_frames=2, embed_dim=384, num_heads=6, depth=1)
     B, N, D = 3, cfg.num_patches, cfg.embed_dim
     shapes = {k: v for k, v in ref_cpu.param_shapes(cfg).items() if k.startswith("blocks.0.")}
@@ -239,10 +240,12 @@ def test_drop_path_matches_oracle_with_the_same_masks():
 
 @pytest.mark.parametrize("kw", [dict(embed_dim=1024, num_heads=16, depth=2, all_frames=4),            # ViT-L width (BASELINE config 4)
                                 dict(embed_dim=768, num_heads=12, depth=1, all_frames=4, img_size=320),   # 320^2 frames (config 5 geometry)
-                                dict(embed_dim=384, num_heads=6, depth=2, all_frames=2, num_latents=3, agg_depth=3)])
+                                dict(embed_dim=384, num_heads=6, depth=2, all_frames=2, num_latents=3, agg_depth=3),
+                                dict(embed_dim=384, num_heads=6, depth=2, all_frames=2, num_latents=5, agg_depth=2),       # 5 slots: the unfolded AggBlockFn, tied ...
+                                dict(embed_dim=384, num_heads=6, depth=2, all_frames=2, num_latents=5, agg_depth=2, agg_weights_tie=False)])   # ... and one weight set per layer
 def test_fp32_step_matches_oracle_other_geometries(kw):
-    """geometries the goldens do not cover (ViT-L width, 320x320 frames -> 400-cell mask grid, 3 slots): HIP fp32 vs the CPU oracle
-    on the same formula weights/inputs, outputs + loss + every gradient"""
+    """geometries the goldens do not cover (ViT-L width, 320x320 frames -> 400-cell mask grid, 3 slots, 5 slots: more than the folded slot attention
+    takes, so the unfolded form runs): HIP fp32 vs the CPU oracle on the same formula weights/inputs, outputs + loss + every gradient"""
     from functools import partial
     from devias_amd.modeling_slot import VisionTransformer
     from devias_amd.train_loss import TrainLoss

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 3e-2)])
 @pytest.mark.parametrize("C", [765, 466])
 def test_fc_dropout_matches_oracle_with_the_same_mask(dtype, tol, C):
-    from devias_amd.modeling_slot import HeadRegionFn
+    from devias_amd.regions import HeadRegionFn
     R, D, h1, h2, G = 6, 768, 512, 256, 196
     shp = {"hw": (C, D), "hb": (C,), "w0": (h1, D), "b0": (h1,), "w2": (h2, h1), "b2": (h2,), "w4": (G, h2), "b4": (G,)}
     P = {k: synth.param_values("fcdrop." + k, s, seed=3) * (0.05 if k.startswith(("hw", "w")) else 0.1) for k, s in shp.items()}
@@ -107,7 +107,7 @@ def test_step_at_101_action_classes_vs_oracle(dtype, tol_out, tol_grad):
 def test_mlp_head_with_and_without_fc_dropout(dtype, tol, drop):
     """head_type='mlp' (MLPHead fc1 -> ReLU -> fc2, model/modeling_slot.py:23-34) behind nn.Dropout on the head's input (:393), forward and backward against the
     same arithmetic in fp32 autograd with the SAME mask; the mask predictor sees the un-dropped slots (:392)."""
-    from devias_amd.modeling_slot import HeadMlpFn
+    from devias_amd.functions import HeadMlpFn
     R, D, C, h1, h2, G = 6, 768, 765, 512, 256, 196
     shp = {"f1w": (512, D), "f1b": (512,), "f2w": (C, 512), "f2b": (C,), "w0": (h1, D), "b0": (h1,), "w2": (h2, h1), "b2": (h2,), "w4": (G, h2), "b4": (G,)}
     P = {k: synth.param_values("mlphead." + k, s, seed=3) * (0.05 if len(s) == 2 else 0.1) for k, s in shp.items()}

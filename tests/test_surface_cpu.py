@@ -41,7 +41,7 @@ def test_weight_cache_invalidation_logic(monkeypatch):
     when invalidate_weight_cache() is called (the fused optimizer and `.data` writers call it: raw-pointer updates do not move the
     version), and entries die with their parameter (no id()-keyed leak)."""
     import gc
-    from devias_amd import modeling_slot as ms, ops
+    from devias_amd import ops, weight_cache as ms
     monkeypatch.setattr(ops, "cast", lambda t, dt, out=None: t.to(dt))            # the GPU cast kernel, stood in for on the CPU
     cache = ms._WeightCache()
     p = torch.nn.Parameter(torch.randn(8, 4))
@@ -190,7 +190,7 @@ def test_gemm_debug_build_compiles(tmp_path):
 def test_published_column_sums_go_stale_safely_with_two_consumers():
     """a residual-stream gradient that carries published column sums and then receives a SECOND consumer's gradient (autograd's
     InputBuffer accumulates it in place into the tagged tensor: same object, same data_ptr) must not hand out the stale sums."""
-    from devias_amd import modeling_slot as ms
+    from devias_amd import functions as ms
     seen = {}
 
     class Producer(torch.autograd.Function):          # stands for a block whose LayerNorm backward publishes colsum(dx) on dx

@@ -1,4 +1,4 @@
-"""Time the ten GEMM calls of one encoder block exactly as modeling_slot.EncoderBlockFn issues them (with their fused epilogues),
+"""Time the ten GEMM calls of one encoder block exactly as functions.EncoderBlockFn issues them (with their fused epilogues),
 M = 50176 (B = 32 clips x 1568 tokens), bf16.  Usage: python tools/gemm_block_shapes.py [ENV=VAL,...]... (one child per set)."""
 import os, sys, subprocess
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
