@@ -1,6 +1,7 @@
 """Per-kernel parity: every C-ABI entry point against a plain PyTorch fp32 statement of the same op (GPU only).
 fp32 kernels are checked tightly (they carry the reference-parity claim); bf16 kernels are checked against the
-fp32 op evaluated on the bf16-rounded inputs, with a bf16-sized tolerance."""
+fp32 op evaluated on the bf16-rounded inputs, with a bf16-sized tolerance.
+The accuracy anchor (per-element bounds against float64 on graded inputs) is tests/test_kernel_bounds_gpu.py; this file pins the kernel forms to each other."""
 import math
 
 import pytest
