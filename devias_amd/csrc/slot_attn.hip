@@ -836,6 +836,7 @@ extern "C" int devias_slot_attn_fwd(const void* q, const void* kv, float* attn, 
         hipLaunchKernelGGL((slot_fwd_finish_kernel<float>), dim3(B * h * S), dim3(256), 0, st, ws_r, ws_o, rsum, (float*)o, S, h, nchunks);
     }
     DEVIAS_CHECK_LAUNCH("devias_slot_attn_fwd(finish)");
+    devias_count(DEVIAS_CNT_SLOT);
     return DEVIAS_OK;
 }
 
@@ -867,6 +868,7 @@ extern "C" int devias_slot_attn_bwd(const void* q, const void* kv, const float* 
         hipLaunchKernelGGL((slot_bwd_finish_kernel<float>), dim3(B * h * S), dim3(256), 0, st, ws, (float*)dq, S, h, nchunks);
     }
     DEVIAS_CHECK_LAUNCH("devias_slot_attn_bwd(finish)");
+    devias_count(DEVIAS_CNT_SLOT);
     return DEVIAS_OK;
 }
 
@@ -885,6 +887,7 @@ extern "C" int devias_slot_attn_kv_grad(const void* q_stack, const void* do_stac
         hipLaunchKernelGGL((slot_kv_grad_kernel<float>), grid, block, 0, st, (const float*)q_stack, (const float*)do_stack, ds_stack,
                            attn_stack, rsum_stack, (float*)dkv, L, B, S, N, h, scale);
     DEVIAS_CHECK_LAUNCH("devias_slot_attn_kv_grad");
+    devias_count(DEVIAS_CNT_SLOT);
     return DEVIAS_OK;
 }
 
@@ -941,6 +944,7 @@ extern "C" int devias_slotf_fwd(const void* qp, const void* ctx, float* attn, fl
         DEVIAS_CHECK_LAUNCH("devias_slotf_fwd(mfma)");
         hipLaunchKernelGGL((slotf_fwd_finish_kernel<bf16>), dim3(B * h * S), dim3(D <= 1024 ? (D + 63) / 64 * 64 : 256), 0, st, ws_r, ws_z, rsum, (bf16*)z, S, h, D, nchunks);
         DEVIAS_CHECK_LAUNCH("devias_slotf_fwd(finish)");
+        devias_count(DEVIAS_CNT_SLOTM);
         return DEVIAS_OK;
     }
     dim3 grid(nchunks, B * h), block(256);
@@ -954,6 +958,7 @@ extern "C" int devias_slotf_fwd(const void* qp, const void* ctx, float* attn, fl
         hipLaunchKernelGGL((slotf_fwd_finish_kernel<float>), dim3(B * h * S), dim3(256), 0, st, ws_r, ws_z, rsum, (float*)z, S, h, D, nchunks);
     }
     DEVIAS_CHECK_LAUNCH("devias_slotf_fwd(finish)");
+    devias_count(DEVIAS_CNT_SLOTF_VALU);
     return DEVIAS_OK;
 }
 
@@ -975,6 +980,7 @@ extern "C" int devias_slotf_bwd(const void* ctx, const float* attn, const float*
         DEVIAS_CHECK_LAUNCH("devias_slotf_bwd(mfma)");
         hipLaunchKernelGGL((slotf_bwd_finish_kernel<bf16>), dim3(B * h * S), dim3(D <= 1024 ? (D + 63) / 64 * 64 : 256), 0, st, ws, (bf16*)dqp, S, h, D, nchunks);
         DEVIAS_CHECK_LAUNCH("devias_slotf_bwd(finish)");
+        devias_count(DEVIAS_CNT_SLOTM);
         return DEVIAS_OK;
     }
     dim3 grid(nchunks, B * h), block(256);
@@ -988,6 +994,7 @@ extern "C" int devias_slotf_bwd(const void* ctx, const float* attn, const float*
         hipLaunchKernelGGL((slotf_bwd_finish_kernel<float>), dim3(B * h * S), dim3(256), 0, st, ws, (float*)dqp, S, h, D, nchunks);
     }
     DEVIAS_CHECK_LAUNCH("devias_slotf_bwd(finish)");
+    devias_count(DEVIAS_CNT_SLOTF_VALU);
     return DEVIAS_OK;
 }
 

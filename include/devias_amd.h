@@ -45,7 +45,8 @@ extern "C" {
 
 int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimizer entry points, 120 = devias_fame_*, 130 = counters + options,
                                     140 = (stream-K GEMM schedule, retired in 160; devias_gemm_args grew by sk_ws / sk_ws_bytes: recompile callers), devias_allreduce_bucket,
-                                    150 = fused regions (devias_encoder_block_* / devias_agg_block_* / devias_head_*), devias_range_* */
+                                    150 = fused regions (devias_encoder_block_* / devias_agg_block_* / devias_head_*), devias_range_*,
+                                    169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
  * Tests use them to ASSERT that the kernels a parity claim is made for are the kernels that ran (the reference has no analogue:
@@ -74,6 +75,10 @@ const char* devias_last_error(void);
 #define DEVIAS_CNT_DKDV2W 18         /* the two-waves-per-SIMD kernel of rounds 2-4 (attention dropout, ws = NULL, option attn_dkdv = 0) */
 #define DEVIAS_CNT_MHSA_QPRE 19      /* bf16 attention calls (forward or backward) served with DEVIAS_ATTN_Q_PRESCALED (ABI 167): 2 per encoder block and step in the measured path */
 #define DEVIAS_CNT_LOSS_LABELS 20    /* devias_head_match_loss_labels_fwd / _bwd calls (ABI 168): 2 per step whose loss was served by the ground-truth-label kernels */
+/* which kernel family served a slot cross-attention call (ABI 169): the accuracy tests assert it per call */
+#define DEVIAS_CNT_SLOTM 21          /* devias_slotf_fwd / _bwd calls served by the matrix-core kernel (slotm_kernel: bf16, S in {1,2,4}, h S <= 16, D in {512,768,1024}) */
+#define DEVIAS_CNT_SLOTF_VALU 22     /* devias_slotf_fwd / _bwd calls served by the VALU kernels (slotf_fwd_kernel / slotf_bwd_kernel) */
+#define DEVIAS_CNT_SLOT 23           /* devias_slot_attn_fwd / _bwd / _kv_grad calls (the unfolded form) */
 #define DEVIAS_CNT_MAX 24
 int64_t devias_counter(int32_t id);          /* -1 for an unknown id */
 void devias_counters_reset(void);
