@@ -346,12 +346,64 @@ extern "C" int devias_slot_select(const void* slots_head, int32_t dtype, int32_t
 
 extern "C" int64_t devias_head_match_loss_workspace_bytes(int32_t B) { return (int64_t)B * 5 * 4; }
 
+// ---- the matching loss: one host path per direction for both scene sources ------------------------------------------------------------------
+// LABELS is the kernels' compile-time mode (devias_amd.h): false reads the scene teacher's fp32 logits `teacher`, true the int64 ground-truth
+// labels `scene_target`; the four entry points below pass the other one as null.
+template <bool LABELS>
 static int check_dims(const devias_loss_dims* d, const char* who) {
     if (!d) return devias_set_error(DEVIAS_EINVAL, "%s: null dims", who);
-    if (d->B <= 0 || d->S < 1 || d->S > LMAXS || d->C != d->nb + d->ns || d->D <= 0 || d->G <= 0 || d->N <= 0 || d->nh <= 0)
+    // a label indexes the ns scene columns behind the nb action columns, so with LABELS both halves of the head must exist
+    if (d->B <= 0 || d->S < 1 || d->S > LMAXS || d->C != d->nb + d->ns || d->D <= 0 || d->G <= 0 || d->N <= 0 || d->nh <= 0 ||
+        (LABELS && (d->nb <= 0 || d->ns <= 0)))
         return devias_set_error(DEVIAS_EINVAL, "%s: bad dims B=%d S=%d C=%d nb=%d ns=%d D=%d G=%d N=%d nh=%d", who, d->B, d->S, d->C,
                                 d->nb, d->ns, d->D, d->G, d->N, d->nh);
     if (d->dtype != DEVIAS_BF16 && d->dtype != DEVIAS_F32) return devias_set_error(DEVIAS_EINVAL, "%s: bad dtype %d", who, d->dtype);
+    return DEVIAS_OK;
+}
+
+template <bool LABELS>
+static int loss_fwd_launch(const char* who, const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
+                           const float* attn, const float* teacher, const int64_t* target, const int64_t* scene_target, const float* fg,
+                           const float* fgN, float* out_losses, int32_t* out_match, void* out_logits, float* ws, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_dims<LABELS>(d, who);
+    if (rc) return rc;
+    const void* scene = LABELS ? (const void*)scene_target : (const void*)teacher;
+    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && scene && target && fg && fgN && out_losses && out_match && out_logits && ws,
+                   "%s: null pointer", who);
+    if (d->dtype == DEVIAS_BF16)
+        hipLaunchKernelGGL((loss_fwd_kernel<bf16, LABELS>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
+                           (const bf16*)maskp, attn, teacher, target, scene_target, fg, fgN, ws, out_match, (bf16*)out_logits);
+    else
+        hipLaunchKernelGGL((loss_fwd_kernel<float, LABELS>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
+                           (const float*)maskp, attn, teacher, target, scene_target, fg, fgN, ws, out_match, (float*)out_logits);
+    DEVIAS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, ws, d->B, out_losses);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return devias_set_error(DEVIAS_ELAUNCH, "%s(final): launch failed: %s", who, hipGetErrorString(e));
+    return DEVIAS_OK;
+}
+
+template <bool LABELS>
+static int loss_bwd_launch(const char* who, const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
+                           const float* attn, const float* teacher, const int64_t* target, const int64_t* scene_target, const float* fg,
+                           const float* fgN, const int32_t* match, const float* g_total, void* d_slots_head, void* d_slots, void* d_maskp,
+                           float* d_attn, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_dims<LABELS>(d, who);
+    if (rc) return rc;
+    const void* scene = LABELS ? (const void*)scene_target : (const void*)teacher;
+    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && scene && target && fg && fgN && match && g_total && d_slots_head && d_slots &&
+                   d_maskp && d_attn, "%s: null pointer", who);
+    if (d->dtype == DEVIAS_BF16)
+        hipLaunchKernelGGL((loss_bwd_kernel<bf16, LABELS>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
+                           (const bf16*)maskp, attn, teacher, target, scene_target, fg, fgN, match, g_total, (bf16*)d_slots_head,
+                           (bf16*)d_slots, (bf16*)d_maskp, d_attn);
+    else
+        hipLaunchKernelGGL((loss_bwd_kernel<float, LABELS>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
+                           (const float*)maskp, attn, teacher, target, scene_target, fg, fgN, match, g_total, (float*)d_slots_head,
+                           (float*)d_slots, (float*)d_maskp, d_attn);
+    DEVIAS_CHECK_LAUNCH(who);
     return DEVIAS_OK;
 }
 
@@ -359,92 +411,35 @@ extern "C" int devias_head_match_loss_fwd(const devias_loss_dims* d, const void*
                                           const float* attn, const float* teacher, const int64_t* target, const float* fg,
                                           const float* fgN, float* out_losses, int32_t* out_match, void* out_logits, float* ws,
                                           void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    int rc = check_dims(d, "devias_head_match_loss_fwd");
-    if (rc) return rc;
-    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && teacher && target && fg && fgN && out_losses && out_match && out_logits && ws,
-                   "devias_head_match_loss_fwd: null pointer");
-    if (d->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((loss_fwd_kernel<bf16, false>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
-                           (const bf16*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, ws, out_match, (bf16*)out_logits);
-    else
-        hipLaunchKernelGGL((loss_fwd_kernel<float, false>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
-                           (const float*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, ws, out_match, (float*)out_logits);
-    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_fwd");
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, ws, d->B, out_losses);
-    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_fwd(final)");
-    return DEVIAS_OK;
+    return loss_fwd_launch<false>("devias_head_match_loss_fwd", d, slots_head, slots, maskp, attn, teacher, target, nullptr, fg, fgN,
+                                  out_losses, out_match, out_logits, ws, stream);
 }
 
 extern "C" int devias_head_match_loss_bwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
                                           const float* attn, const float* teacher, const int64_t* target, const float* fg,
                                           const float* fgN, const int32_t* match, const float* g_total, void* d_slots_head,
                                           void* d_slots, void* d_maskp, float* d_attn, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    int rc = check_dims(d, "devias_head_match_loss_bwd");
-    if (rc) return rc;
-    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && teacher && target && fg && fgN && match && g_total && d_slots_head &&
-                   d_slots && d_maskp && d_attn, "devias_head_match_loss_bwd: null pointer");
-    if (d->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((loss_bwd_kernel<bf16, false>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
-                           (const bf16*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, match, g_total, (bf16*)d_slots_head, (bf16*)d_slots,
-                           (bf16*)d_maskp, d_attn);
-    else
-        hipLaunchKernelGGL((loss_bwd_kernel<float, false>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
-                           (const float*)maskp, attn, teacher, target, (const int64_t*)nullptr, fg, fgN, match, g_total, (float*)d_slots_head, (float*)d_slots,
-                           (float*)d_maskp, d_attn);
-    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_bwd");
-    return DEVIAS_OK;
+    return loss_bwd_launch<false>("devias_head_match_loss_bwd", d, slots_head, slots, maskp, attn, teacher, target, nullptr, fg, fgN,
+                                  match, g_total, d_slots_head, d_slots, d_maskp, d_attn, stream);
 }
 
-// ---- ground-truth scene labels: the LABELS mode of the two kernels above (devias_amd.h) ----------------------------------------------------
-static int check_label_dims(const devias_loss_dims* d, const char* who) {
-    int rc = check_dims(d, who);
-    if (rc) return rc;
-    if (d->nb <= 0 || d->ns <= 0) return devias_set_error(DEVIAS_EINVAL, "%s: bad dims nb=%d ns=%d (both must be positive)", who, d->nb, d->ns);
-    return DEVIAS_OK;
-}
-
+// ground-truth scene labels: counted (DEVIAS_CNT_LOSS_LABELS) once per launch that went out
 extern "C" int devias_head_match_loss_labels_fwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
                                                  const float* attn, const int64_t* target, const int64_t* scene_target, const float* fg,
                                                  const float* fgN, float* out_losses, int32_t* out_match, void* out_logits, float* ws,
                                                  void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    int rc = check_label_dims(d, "devias_head_match_loss_labels_fwd");
-    if (rc) return rc;
-    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && target && scene_target && fg && fgN && out_losses && out_match && out_logits && ws,
-                   "devias_head_match_loss_labels_fwd: null pointer");
-    if (d->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((loss_fwd_kernel<bf16, true>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
-                           (const bf16*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, ws, out_match, (bf16*)out_logits);
-    else
-        hipLaunchKernelGGL((loss_fwd_kernel<float, true>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
-                           (const float*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, ws, out_match, (float*)out_logits);
-    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_labels_fwd");
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, ws, d->B, out_losses);
-    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_labels_fwd(final)");
-    devias_count(DEVIAS_CNT_LOSS_LABELS);
-    return DEVIAS_OK;
+    int rc = loss_fwd_launch<true>("devias_head_match_loss_labels_fwd", d, slots_head, slots, maskp, attn, nullptr, target, scene_target, fg,
+                                   fgN, out_losses, out_match, out_logits, ws, stream);
+    if (rc == DEVIAS_OK) devias_count(DEVIAS_CNT_LOSS_LABELS);
+    return rc;
 }
 
 extern "C" int devias_head_match_loss_labels_bwd(const devias_loss_dims* d, const void* slots_head, const void* slots, const void* maskp,
                                                  const float* attn, const int64_t* target, const int64_t* scene_target, const float* fg,
                                                  const float* fgN, const int32_t* match, const float* g_total, void* d_slots_head,
                                                  void* d_slots, void* d_maskp, float* d_attn, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    int rc = check_label_dims(d, "devias_head_match_loss_labels_bwd");
-    if (rc) return rc;
-    DEVIAS_REQUIRE(slots_head && slots && maskp && attn && target && scene_target && fg && fgN && match && g_total && d_slots_head &&
-                   d_slots && d_maskp && d_attn, "devias_head_match_loss_labels_bwd: null pointer");
-    if (d->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((loss_bwd_kernel<bf16, true>), dim3(d->B), dim3(256), 0, st, *d, (const bf16*)slots_head, (const bf16*)slots,
-                           (const bf16*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, match, g_total, (bf16*)d_slots_head,
-                           (bf16*)d_slots, (bf16*)d_maskp, d_attn);
-    else
-        hipLaunchKernelGGL((loss_bwd_kernel<float, true>), dim3(d->B), dim3(256), 0, st, *d, (const float*)slots_head, (const float*)slots,
-                           (const float*)maskp, attn, (const float*)nullptr, target, scene_target, fg, fgN, match, g_total, (float*)d_slots_head,
-                           (float*)d_slots, (float*)d_maskp, d_attn);
-    DEVIAS_CHECK_LAUNCH("devias_head_match_loss_labels_bwd");
-    devias_count(DEVIAS_CNT_LOSS_LABELS);
-    return DEVIAS_OK;
+    int rc = loss_bwd_launch<true>("devias_head_match_loss_labels_bwd", d, slots_head, slots, maskp, attn, nullptr, target, scene_target, fg,
+                                   fgN, match, g_total, d_slots_head, d_slots, d_maskp, d_attn, stream);
+    if (rc == DEVIAS_OK) devias_count(DEVIAS_CNT_LOSS_LABELS);
+    return rc;
 }

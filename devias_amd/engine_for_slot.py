@@ -24,42 +24,24 @@ def train_class_batch(model, scene_model, samples, target, train_criterion, fg_m
     return total_loss, output, loss_dict
 
 
-def train_one_epoch(model, scene_model, train_criterion, data_loader: Iterable, optimizer, device, epoch: int,
-                    max_norm: float = 0, start_steps: int = 0, lr_schedule_values=None, wd_schedule_values=None,
-                    num_training_steps_per_epoch: Optional[int] = None, update_freq: int = 1, mask_model=None,
-                    grad_sync=None, check_finite_every: int = 50, log_every: int = 100):
-    """engine/engine_for_slot.py:64-214 restated for this stack: LR/WD schedule poke (:91-96), H2D (:98-99), mask model
-    (:106-108), train_class_batch, backward, optional gradient all-reduce (`grad_sync`, devias_amd.parallel), optimizer step.
-    The per-step `loss.item()` finite check (:140-144) and `torch.cuda.synchronize()` (:171) are replaced by one
-    host check every `check_finite_every` steps."""
-    model.train(True)
-    if not torch.is_tensor(scene_model):
-        scene_model.eval()
+def _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch, update_freq, grad_sync, check_finite_every):
+    """The part of train_one_epoch that does not depend on the recipe (shared with engine_for_slot_hvu): LR/WD schedule poke, gradient accumulation over
+    `update_freq` micro-batches, optional gradient all-reduce (`grad_sync`, devias_amd.parallel), clip + optimizer step, and one host check of the loss
+    every `check_finite_every` micro-batches.  `step(batch) -> (loss, loss_dict)` is the recipe: H2D copies, mask model, train_class_batch."""
     optimizer.zero_grad(set_to_none=True)
-    stats = {}
-    n_steps = 0
-    grad_norm = None
+    stats, grad_norm = {}, None
     for data_iter_step, batch in enumerate(data_loader):
-        samples, targets = batch[0], batch[1]
-        step = data_iter_step // update_freq
-        if num_training_steps_per_epoch is not None and step >= num_training_steps_per_epoch:
+        it = data_iter_step // update_freq
+        if num_training_steps_per_epoch is not None and it >= num_training_steps_per_epoch:
             continue
-        it = start_steps + step
+        it += start_steps
         if (lr_schedule_values is not None or wd_schedule_values is not None) and data_iter_step % update_freq == 0:
             for group in optimizer.param_groups:
                 if lr_schedule_values is not None:
                     group["lr"] = lr_schedule_values[it] * group.get("lr_scale", 1.0)
                 if wd_schedule_values is not None and group["weight_decay"] > 0:
                     group["weight_decay"] = wd_schedule_values[it]
-        samples = samples.to(device, non_blocking=True)
-        targets = targets.to(device, non_blocking=True)
-        if mask_model is not None:
-            samples, targets, masks = mask_model(samples, targets)
-        else:
-            masks = batch[2]
-            masks = tuple(m.to(device, non_blocking=True) for m in masks)
-        teacher = scene_model if not torch.is_tensor(scene_model) else scene_model
-        loss, output, loss_dict = train_class_batch(model, teacher, samples, targets, train_criterion, fg_mask=masks)
+        loss, loss_dict = step(batch)
         if update_freq > 1:
             loss = loss / update_freq
         if grad_sync is not None:
@@ -78,38 +60,60 @@ def train_one_epoch(model, scene_model, train_criterion, data_loader: Iterable, 
                     grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
                 optimizer.step()
             optimizer.zero_grad(set_to_none=True)
-        n_steps += 1
-        if check_finite_every and n_steps % check_finite_every == 0:
+        if check_finite_every and (data_iter_step + 1) % check_finite_every == 0:          # skipped batches only follow, so this counts the ones run
             loss_value = float(loss.detach().float().sum())
             if not math.isfinite(loss_value):
                 print("Loss is {}, stopping training".format(loss_value))
                 sys.exit(1)
-            stats["loss"] = loss_value
             if grad_norm is not None:
                 stats["grad_norm"] = float(grad_norm)
-            stats["lr"] = max(g["lr"] for g in optimizer.param_groups)
-            stats["min_lr"] = min(g["lr"] for g in optimizer.param_groups)
-            stats.update({k: float(v) for k, v in loss_dict.items()})
+            stats.update(loss=loss_value, lr=max(g["lr"] for g in optimizer.param_groups), min_lr=min(g["lr"] for g in optimizer.param_groups), **{k: float(v) for k, v in loss_dict.items()})
     return stats
+
+
+def train_one_epoch(model, scene_model, train_criterion, data_loader: Iterable, optimizer, device, epoch: int,
+                    max_norm: float = 0, start_steps: int = 0, lr_schedule_values=None, wd_schedule_values=None,
+                    num_training_steps_per_epoch: Optional[int] = None, update_freq: int = 1, mask_model=None,
+                    grad_sync=None, check_finite_every: int = 50, log_every: int = 100):
+    """engine/engine_for_slot.py:64-214 restated for this stack: LR/WD schedule poke (:91-96), H2D (:98-99), mask model (:106-108), train_class_batch,
+    backward, optional gradient all-reduce, optimizer step (_run_steps).  The per-step `loss.item()` finite check (:140-144) and
+    `torch.cuda.synchronize()` (:171) are replaced by one host check every `check_finite_every` steps."""
+    model.train(True)
+    if not torch.is_tensor(scene_model):
+        scene_model.eval()
+
+    def step(batch):
+        samples, targets = (t.to(device, non_blocking=True) for t in batch[:2])
+        if mask_model is not None:
+            samples, targets, masks = mask_model(samples, targets)
+        else:
+            masks = tuple(m.to(device, non_blocking=True) for m in batch[2])
+        loss, _output, loss_dict = train_class_batch(model, scene_model, samples, targets, train_criterion, fg_mask=masks)
+        return loss, loss_dict
+
+    return _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch,
+                      update_freq, grad_sync, check_finite_every)
+
+
+def _evaluate(data_loader, model, device, n_fields, names, per_batch):
+    """One eval-mode pass, shared by every validation loop of both recipes: the first `n_fields` fields of a batch go to the device, the model runs on field 0,
+    and `per_batch(model output, device fields, batch)` returns float64 [n, sum of CE, one hit count per name].  The sums stay on the device; one host read at
+    the end of the loader (the reference reads three scalars per batch).  -> {'loss', *names} as sample-weighted means (the hit counts in percent)"""
+    model.eval()
+    acc = torch.zeros(2 + len(names), dtype=torch.float64, device=device)
+    for batch in data_loader:
+        fields = [f.to(device, non_blocking=True) for f in batch[:n_fields]]
+        acc += per_batch(model(fields[0]), fields, batch)
+    vals = acc.tolist()
+    n = max(vals[0], 1.0)
+    return {"loss": vals[1] / n, **{k: 100.0 * h / n for k, h in zip(names, vals[2:])}}
 
 
 @torch.no_grad()
 def validation_one_epoch(data_loader, model, device, topk=(1, 5)):
     """engine/engine_for_slot.py:215-250: eval-mode forward, cross-entropy of the selected action logits [B, nb + ns] against
-    the action target, top-1 / top-5 accuracy.  Sums are kept on the device; one host read at the end of the loader (the
-    reference reads three scalars per batch).  Returns {'loss', 'acc1', 'acc5'} as sample-weighted means (acc in percent)."""
-    model.eval()
-    acc = torch.zeros(2 + len(topk), dtype=torch.float64, device=device)          # [n, sum of CE, hits@k...]
-    for batch in data_loader:
-        videos = batch[0].to(device, non_blocking=True)
-        target = batch[1].to(device, non_blocking=True)
-        _, (output, _scene_output, _attn), _ = model(videos)
-        acc += _batch_metrics(output.float(), target, topk)
-    n, ce, hits = float(acc[0]), float(acc[1]), [float(v) for v in acc[2:]]
-    out = {"loss": ce / max(n, 1.0)}
-    for k, h in zip(topk, hits):
-        out["acc%d" % k] = 100.0 * h / max(n, 1.0)
-    return out
+    the action target, top-1 / top-5 accuracy.  Returns {'loss', 'acc1', 'acc5'} as sample-weighted means (acc in percent)."""
+    return _evaluate(data_loader, model, device, 2, ["acc%d" % k for k in topk], lambda out, f, _: _batch_metrics(out[1][0].float(), f[1], topk))
 
 
 def _batch_metrics(output, target, topk):
@@ -128,22 +132,18 @@ def _batch_metrics(output, target, topk):
 def final_test(data_loader, model, device, file):
     """engine/engine_for_slot.py:253-303: as validation, and one line `id [logits] target chunk split` per sample written to
     `file` after a first line with the LAST batch's `acc1, acc5` (the reference writes exactly that)."""
-    model.eval()
-    acc = torch.zeros(4, dtype=torch.float64, device=device)
-    lines, last = [], (0.0, 0.0)
-    for batch in data_loader:
-        videos = batch[0].to(device, non_blocking=True)
-        target = batch[1].to(device, non_blocking=True)
-        ids, chunk_nb, split_nb = batch[2], batch[3], batch[4]
-        _, (output, _scene_output, _attn), _ = model(videos)
-        m = _batch_metrics(output.float(), target, (1, 5))
-        acc += m
-        rows, tgt, mh = output.float().cpu().numpy(), target.cpu().numpy(), m.cpu().numpy()
-        last = (100.0 * mh[2] / mh[0], 100.0 * mh[3] / mh[0])
-        for i in range(rows.shape[0]):
-            lines.append("{} {} {} {} {}\n".format(ids[i], str(rows[i].tolist()), str(int(tgt[i])), str(int(chunk_nb[i])), str(int(split_nb[i]))))
+    lines = ["0.0, 0.0\n"]
+
+    def per_batch(out, fields, batch):
+        output, target = out[1][0].float(), fields[1]
+        m = _batch_metrics(output, target, (1, 5))
+        rows, tgt, mh = output.cpu().numpy(), target.cpu().numpy(), m.cpu().numpy()
+        lines[0] = "{}, {}\n".format(100.0 * mh[2] / mh[0], 100.0 * mh[3] / mh[0])
+        for i, (sample_id, chunk_nb, split_nb) in enumerate(zip(*batch[2:5])):
+            lines.append("{} {} {} {} {}\n".format(sample_id, str(rows[i].tolist()), str(int(tgt[i])), str(int(chunk_nb)), str(int(split_nb))))
+        return m
+
+    stats = _evaluate(data_loader, model, device, 2, ["acc1", "acc5"], per_batch)
     with open(file, "w") as f:
-        f.write("{}, {}\n".format(last[0], last[1]))
         f.writelines(lines)
-    n = max(float(acc[0]), 1.0)
-    return {"loss": float(acc[1]) / n, "acc1": 100.0 * float(acc[2]) / n, "acc5": 100.0 * float(acc[3]) / n}
+    return stats

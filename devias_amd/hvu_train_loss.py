@@ -5,34 +5,11 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-from torch.autograd import Function
 
-from . import ops
-from .train_loss import LOSS_NAMES
+from .train_loss import LOSS_NAMES, _matching_loss  # noqa: F401   (LOSS_NAMES: part of this module's surface)
 
 HVU_NUM_ACTION_CLASSES = 739          # run_slot_finetuning_hvu.py:35-36
 HVU_NUM_SCENE_CLASSES = 248
-
-
-class HeadMatchLossLabelsFn(Function):
-    @staticmethod
-    def forward(ctx, slots_head, slots, maskp, attn, target, scene_target, fg, fgN, nb, w_mp, w_md, scene_ce=False):
-        slots_head, slots, maskp, attn = (t.contiguous() for t in (slots_head, slots, maskp, attn))
-        losses, match, logits = ops.head_match_loss_labels_fwd(slots_head, slots, maskp, attn, target, scene_target, fg, fgN, nb, w_mp, w_md, scene_ce)
-        ctx.saved = (slots_head, slots, maskp, attn, target, scene_target, fg, fgN, match)
-        ctx.w = (nb, w_mp, w_md, scene_ce)
-        ctx.mark_non_differentiable(losses, match, logits)
-        total = losses[5:6].clone()
-        return total, losses, match, logits
-
-    @staticmethod
-    def backward(ctx, g_total, *_):
-        slots_head, slots, maskp, attn, target, scene_target, fg, fgN, match = ctx.saved
-        nb, w_mp, w_md, scene_ce = ctx.w
-        g = g_total.reshape(1).float().contiguous()
-        dZ, dslots, dmask, dattn = ops.head_match_loss_labels_bwd(slots_head, slots, maskp, attn, target, scene_target, fg, fgN, match, g,
-                                                                  nb, w_mp, w_md, scene_ce)
-        return dZ, dslots, dmask, dattn, None, None, None, None, None, None, None, None
 
 
 class TrainLoss(nn.Module):
@@ -67,22 +44,8 @@ class TrainLoss(nn.Module):
         self.last_match = None
 
     def forward(self, student_output, action_targets, scene_targets, fg_mask=None):
-        _, (_, _, attn), (slots_head, slots, mask_predictions) = student_output
+        slots_head = student_output[2][0]
         if slots_head.shape[1] != self.num_action_classes + self.num_scene_classes:
             raise ValueError(f"head width {slots_head.shape[1]} != num_action_classes {self.num_action_classes} + num_scene_classes {self.num_scene_classes}")
-        fg, fgN = fg_mask
-        dev = slots_head.device
-        fg = fg.to(device=dev, dtype=torch.float32).contiguous()       # k/256 masks: the reference's .half() is value-preserving
-        fgN = fgN.to(device=dev, dtype=torch.float32).contiguous()
-        target = action_targets.to(device=dev, dtype=torch.int64).contiguous()
-        scene_target = scene_targets.to(device=dev, dtype=torch.int64).contiguous()       # read only: never offset in place
-        total, losses, match, logits = HeadMatchLossLabelsFn.apply(
-            slots_head, slots, mask_predictions, attn, target, scene_target, fg, fgN, self.num_action_classes,
-            self.mask_prediction_loss_weight, self.mask_distill_loss_weight, self.scene_criterion == "CE")
-        self.last_match = match
-        if self.sync_loss_dict:
-            vals = losses.tolist()
-            loss_dict = {k: vals[i] for i, k in enumerate(LOSS_NAMES)}
-        else:
-            loss_dict = {k: losses[i] for i, k in enumerate(LOSS_NAMES)}
-        return total, logits, loss_dict
+        scene_target = scene_targets.to(device=slots_head.device, dtype=torch.int64).contiguous()       # read only: never offset in place
+        return _matching_loss(self, student_output, scene_target, action_targets, fg_mask, 0.0)       # no scene weight in this recipe

@@ -473,12 +473,12 @@ def slot_select(slots_head: torch.Tensor, B: int, S: int, nb: int) -> torch.Tens
     return idx
 
 
-def _loss_dims(slots_head, slots, maskp, attn, teacher, B, nb, w_scene, w_mp, w_md, scene_ce=False):
+def _loss_dims(slots_head, slots, maskp, attn, B, nb, ns, w_scene, w_mp, w_md, scene_ce=False):
     d = _lib.LossDims()
     d.B = B
     d.S = slots_head.shape[0] // B
     d.C = slots_head.shape[1]
-    d.nb, d.ns = nb, teacher.shape[1]
+    d.nb, d.ns = nb, ns
     d.D, d.G, d.N = slots.shape[1], maskp.shape[1], attn.shape[2]
     d.nh = attn.shape[0] // B
     d.w_scene, d.w_mask_pred, d.w_mask_distill = w_scene, w_mp, w_md
@@ -487,99 +487,78 @@ def _loss_dims(slots_head, slots, maskp, attn, teacher, B, nb, w_scene, w_mp, w_
     return d
 
 
-def head_match_loss_fwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce=False):
-    B = target.shape[0]
+def _chk_loss(who, slots_head, slots, maskp, attn, scene, labels, target, fg, fgN, nb):
+    """The kernels index every tensor from B, S, C, nb, D, G, N and nh alone, so tensors whose rows disagree are refused here, before anything is launched,
+    rather than read out of bounds on the device.  `scene` is the int64 labels [B] if `labels`, else the teacher's fp32 logits [B, C - nb]."""
+    sname = "scene_target" if labels else "teacher"
     for t, n, dt in ((slots_head, "slots_head", None), (slots, "slots", slots_head.dtype), (maskp, "maskp", slots_head.dtype),
-                     (attn, "attn", torch.float32), (teacher, "teacher", torch.float32), (target, "target", torch.int64),
+                     (attn, "attn", torch.float32), (target, "target", torch.int64), (scene, sname, torch.int64 if labels else torch.float32),
                      (fg, "fg", torch.float32), (fgN, "fgN", torch.float32)):
-        _chk(t, "head_match_loss_fwd." + n, dt)
-    d = _loss_dims(slots_head, slots, maskp, attn, teacher, B, nb, w_scene, w_mp, w_md, scene_ce)
+        _chk(t, who + "." + n, dt)
+    B, rows = target.shape[0], slots_head.shape[0]
+    if target.dim() != 1 or scene.shape != ((B,) if labels else (B, slots_head.shape[1] - nb)) or B == 0 or rows % B or slots.shape[0] != rows \
+            or maskp.shape[0] != rows or attn.dim() != 3 or attn.shape[0] % B or attn.shape[1] != rows // B or fg.shape != (B, maskp.shape[1]) \
+            or fgN.shape != (B, attn.shape[2]):
+        raise ValueError(f"{who}: inconsistent shapes slots_head {tuple(slots_head.shape)} slots {tuple(slots.shape)} maskp {tuple(maskp.shape)} attn {tuple(attn.shape)} "
+                         f"target {tuple(target.shape)} {sname} {tuple(scene.shape)} fg {tuple(fg.shape)} fgN {tuple(fgN.shape)} nb {nb}")
+    return B
+
+
+def _loss_entry(direction, slots_head, slots, maskp, attn, scene, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce):
+    """The one place that branches on the recipe, by the scene source's dtype (the kernels' LABELS flag): int64 labels go to the label entry points, which
+    take (target, scene_target) where the teacher ones take (teacher, target) and ignore w_scene.  -> (who, B, dims, the ten leading arguments)"""
+    labels = scene.dtype == torch.int64
+    who = ("head_match_loss_labels_" if labels else "head_match_loss_") + direction
+    B = _chk_loss(who, slots_head, slots, maskp, attn, scene, labels, target, fg, fgN, nb)
+    d = _loss_dims(slots_head, slots, maskp, attn, B, nb, slots_head.shape[1] - nb, 0.0 if labels else w_scene, w_mp, w_md, scene_ce)
+    lead = (slots_head, slots, maskp, attn) + ((target, scene) if labels else (scene, target)) + (fg, fgN)
+    return who, B, d, (ctypes.byref(d),) + tuple(t.data_ptr() for t in lead)
+
+
+def _head_match_loss_fwd(slots_head, slots, maskp, attn, scene, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce=False):
+    who, B, d, lead = _loss_entry("fwd", slots_head, slots, maskp, attn, scene, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce)
     dev = slots_head.device
     losses = torch.empty((6,), dtype=torch.float32, device=dev)
     match = torch.empty((B, 2), dtype=torch.int32, device=dev)
     logits = torch.empty((B, d.C), dtype=slots_head.dtype, device=dev)
     ws = workspace(_lib.load().devias_head_match_loss_workspace_bytes(B), dev)
-    _lib.check(_lib.load().devias_head_match_loss_fwd(ctypes.byref(d), slots_head.data_ptr(), slots.data_ptr(), maskp.data_ptr(),
-                                                      attn.data_ptr(), teacher.data_ptr(), target.data_ptr(), fg.data_ptr(),
-                                                      fgN.data_ptr(), losses.data_ptr(), match.data_ptr(), logits.data_ptr(),
-                                                      ws.data_ptr(), _stream()), "devias_head_match_loss_fwd")
+    _lib.check(getattr(_lib.load(), "devias_" + who)(*lead, losses.data_ptr(), match.data_ptr(), logits.data_ptr(), ws.data_ptr(), _stream()), "devias_" + who)
     return losses, match, logits
 
 
-def head_match_loss_bwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, match, g_total, nb, w_scene, w_mp, w_md, scene_ce=False):
-    B = target.shape[0]
-    _chk(g_total, "head_match_loss_bwd.g_total", torch.float32)
-    d = _loss_dims(slots_head, slots, maskp, attn, teacher, B, nb, w_scene, w_mp, w_md, scene_ce)
+def _head_match_loss_bwd(slots_head, slots, maskp, attn, scene, target, fg, fgN, match, g_total, nb, w_scene, w_mp, w_md, scene_ce=False):
+    who, B, d, lead = _loss_entry("bwd", slots_head, slots, maskp, attn, scene, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce)
+    _chk(g_total, who + ".g_total", torch.float32)
+    _chk(match, who + ".match", torch.int32)
     dZ = torch.empty_like(slots_head)
     dslots = torch.empty_like(slots)
     dmask = torch.empty_like(maskp)
     dattn = torch.empty_like(attn)
-    _lib.check(_lib.load().devias_head_match_loss_bwd(ctypes.byref(d), slots_head.data_ptr(), slots.data_ptr(), maskp.data_ptr(),
-                                                      attn.data_ptr(), teacher.data_ptr(), target.data_ptr(), fg.data_ptr(),
-                                                      fgN.data_ptr(), match.data_ptr(), g_total.data_ptr(), dZ.data_ptr(),
-                                                      dslots.data_ptr(), dmask.data_ptr(), dattn.data_ptr(), _stream()),
-               "devias_head_match_loss_bwd")
+    _lib.check(getattr(_lib.load(), "devias_" + who)(*lead, match.data_ptr(), g_total.data_ptr(), dZ.data_ptr(), dslots.data_ptr(), dmask.data_ptr(),
+                                                     dattn.data_ptr(), _stream()), "devias_" + who)
     return dZ, dslots, dmask, dattn
 
 
-def _loss_label_dims(slots_head, slots, maskp, attn, B, nb, w_mp, w_md, scene_ce=False):
-    d = _lib.LossDims()
-    d.B = B
-    d.S = slots_head.shape[0] // B
-    d.C = slots_head.shape[1]
-    d.nb, d.ns = nb, slots_head.shape[1] - nb
-    d.D, d.G, d.N = slots.shape[1], maskp.shape[1], attn.shape[2]
-    d.nh = attn.shape[0] // B
-    d.w_scene, d.w_mask_pred, d.w_mask_distill = 0.0, w_mp, w_md          # w_scene: ignored by the label entry points
-    d.dtype = dt_code(slots_head.dtype)
-    d.scene_ce = 1 if scene_ce else 0
-    return d
+# the four public wrappers pin their scene argument's dtype (so a mistyped one is a TypeError, not the other recipe) and forward
+def head_match_loss_fwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce=False):
+    _chk(teacher, "head_match_loss_fwd.teacher", torch.float32)
+    return _head_match_loss_fwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce)
 
 
-def _chk_loss_labels(who, slots_head, slots, maskp, attn, target, scene_target, fg, fgN):
-    for t, n, dt in ((slots_head, "slots_head", None), (slots, "slots", slots_head.dtype), (maskp, "maskp", slots_head.dtype),
-                     (attn, "attn", torch.float32), (target, "target", torch.int64), (scene_target, "scene_target", torch.int64),
-                     (fg, "fg", torch.float32), (fgN, "fgN", torch.float32)):
-        _chk(t, who + "." + n, dt)
-    B = target.shape[0]
-    if scene_target.shape != target.shape or B == 0 or slots_head.shape[0] % B or slots.shape[0] != slots_head.shape[0] or maskp.shape[0] != slots_head.shape[0] \
-            or attn.dim() != 3 or attn.shape[0] % B or attn.shape[1] != slots_head.shape[0] // B or fg.shape != (B, maskp.shape[1]) or fgN.shape != (B, attn.shape[2]):
-        raise ValueError(f"{who}: inconsistent shapes slots_head {tuple(slots_head.shape)} slots {tuple(slots.shape)} maskp {tuple(maskp.shape)} attn {tuple(attn.shape)} "
-                         f"target {tuple(target.shape)} scene_target {tuple(scene_target.shape)} fg {tuple(fg.shape)} fgN {tuple(fgN.shape)}")
-    return B
+def head_match_loss_bwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, match, g_total, nb, w_scene, w_mp, w_md, scene_ce=False):
+    _chk(teacher, "head_match_loss_bwd.teacher", torch.float32)
+    return _head_match_loss_bwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, match, g_total, nb, w_scene, w_mp, w_md, scene_ce)
 
 
 def head_match_loss_labels_fwd(slots_head, slots, maskp, attn, target, scene_target, fg, fgN, nb, w_mp, w_md, scene_ce=False):
     """devias_head_match_loss_labels_fwd: the 'matching' loss against ground-truth scene labels (int64 [B] in [0, C - nb), not offset by nb)"""
-    B = _chk_loss_labels("head_match_loss_labels_fwd", slots_head, slots, maskp, attn, target, scene_target, fg, fgN)
-    d = _loss_label_dims(slots_head, slots, maskp, attn, B, nb, w_mp, w_md, scene_ce)
-    dev = slots_head.device
-    losses = torch.empty((6,), dtype=torch.float32, device=dev)
-    match = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    logits = torch.empty((B, d.C), dtype=slots_head.dtype, device=dev)
-    ws = workspace(_lib.load().devias_head_match_loss_workspace_bytes(B), dev)
-    _lib.check(_lib.load().devias_head_match_loss_labels_fwd(ctypes.byref(d), slots_head.data_ptr(), slots.data_ptr(), maskp.data_ptr(),
-                                                             attn.data_ptr(), target.data_ptr(), scene_target.data_ptr(), fg.data_ptr(),
-                                                             fgN.data_ptr(), losses.data_ptr(), match.data_ptr(), logits.data_ptr(),
-                                                             ws.data_ptr(), _stream()), "devias_head_match_loss_labels_fwd")
-    return losses, match, logits
+    _chk(scene_target, "head_match_loss_labels_fwd.scene_target", torch.int64)
+    return _head_match_loss_fwd(slots_head, slots, maskp, attn, scene_target, target, fg, fgN, nb, 0.0, w_mp, w_md, scene_ce)
 
 
 def head_match_loss_labels_bwd(slots_head, slots, maskp, attn, target, scene_target, fg, fgN, match, g_total, nb, w_mp, w_md, scene_ce=False):
-    B = _chk_loss_labels("head_match_loss_labels_bwd", slots_head, slots, maskp, attn, target, scene_target, fg, fgN)
-    _chk(g_total, "head_match_loss_labels_bwd.g_total", torch.float32)
-    _chk(match, "head_match_loss_labels_bwd.match", torch.int32)
-    d = _loss_label_dims(slots_head, slots, maskp, attn, B, nb, w_mp, w_md, scene_ce)
-    dZ = torch.empty_like(slots_head)
-    dslots = torch.empty_like(slots)
-    dmask = torch.empty_like(maskp)
-    dattn = torch.empty_like(attn)
-    _lib.check(_lib.load().devias_head_match_loss_labels_bwd(ctypes.byref(d), slots_head.data_ptr(), slots.data_ptr(), maskp.data_ptr(),
-                                                             attn.data_ptr(), target.data_ptr(), scene_target.data_ptr(), fg.data_ptr(),
-                                                             fgN.data_ptr(), match.data_ptr(), g_total.data_ptr(), dZ.data_ptr(),
-                                                             dslots.data_ptr(), dmask.data_ptr(), dattn.data_ptr(), _stream()),
-               "devias_head_match_loss_labels_bwd")
-    return dZ, dslots, dmask, dattn
+    _chk(scene_target, "head_match_loss_labels_bwd.scene_target", torch.int64)
+    return _head_match_loss_bwd(slots_head, slots, maskp, attn, scene_target, target, fg, fgN, match, g_total, nb, 0.0, w_mp, w_md, scene_ce)
 
 
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):

@@ -12,24 +12,38 @@ LOSS_NAMES = ("action_loss", "scene_loss", "cosine_loss", "mask_prediction_loss"
 
 
 class HeadMatchLossFn(Function):
+    """`scene` is the scene teacher's fp32 logits [B, ns] or int64 ground-truth labels [B] (then `w_scene` is unused): ops picks the entry point from its dtype"""
     @staticmethod
-    def forward(ctx, slots_head, slots, maskp, attn, teacher, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce=False):
+    def forward(ctx, slots_head, slots, maskp, attn, scene, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce=False):
         slots_head, slots, maskp, attn = (t.contiguous() for t in (slots_head, slots, maskp, attn))
-        losses, match, logits = ops.head_match_loss_fwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce)
-        ctx.saved = (slots_head, slots, maskp, attn, teacher, target, fg, fgN, match)
+        losses, match, logits = ops._head_match_loss_fwd(slots_head, slots, maskp, attn, scene, target, fg, fgN, nb, w_scene, w_mp, w_md, scene_ce)
+        ctx.saved = (slots_head, slots, maskp, attn, scene, target, fg, fgN, match)
         ctx.w = (nb, w_scene, w_mp, w_md, scene_ce)
         ctx.mark_non_differentiable(losses, match, logits)
-        total = losses[5:6].clone()
-        return total, losses, match, logits
+        return losses[5:6].clone(), losses, match, logits
 
     @staticmethod
     def backward(ctx, g_total, *_):
-        slots_head, slots, maskp, attn, teacher, target, fg, fgN, match = ctx.saved
-        nb, w_scene, w_mp, w_md, scene_ce = ctx.w
         g = g_total.reshape(1).float().contiguous()
-        dZ, dslots, dmask, dattn = ops.head_match_loss_bwd(slots_head, slots, maskp, attn, teacher, target, fg, fgN, match, g,
-                                                           nb, w_scene, w_mp, w_md, scene_ce)
+        dZ, dslots, dmask, dattn = ops._head_match_loss_bwd(*ctx.saved, g, *ctx.w)
         return dZ, dslots, dmask, dattn, None, None, None, None, None, None, None, None, None
+
+
+def _matching_loss(crit, student_output, scene, target, fg_mask, w_scene):
+    """What both recipes' TrainLoss.forward do once they hold the scene source (teacher logits or labels, already on the device): stage the masks and the action
+    target, one fused launch, `crit.last_match`, and `loss_dict` as Python floats (one device->host copy) or, with sync_loss_dict=False, 0-d device tensors."""
+    _, (_, _, attn), (slots_head, slots, mask_predictions) = student_output
+    fg, fgN = fg_mask
+    dev = slots_head.device
+    fg = fg.to(device=dev, dtype=torch.float32).contiguous()       # k/256 masks: the reference's .half() is value-preserving
+    fgN = fgN.to(device=dev, dtype=torch.float32).contiguous()
+    target = target.to(device=dev, dtype=torch.int64).contiguous()
+    total, losses, match, logits = HeadMatchLossFn.apply(
+        slots_head, slots, mask_predictions, attn, scene, target, fg, fgN, crit.num_action_classes,
+        w_scene, crit.mask_prediction_loss_weight, crit.mask_distill_loss_weight, crit.scene_criterion == "CE")
+    crit.last_match = match
+    vals = losses.tolist() if crit.sync_loss_dict else losses
+    return total, logits, {k: vals[i] for i, k in enumerate(LOSS_NAMES)}
 
 
 class TrainLoss(nn.Module):
@@ -59,21 +73,6 @@ class TrainLoss(nn.Module):
         self.last_match = None
 
     def forward(self, model, student_output, teacher_outputs, target, fg_mask=None):
-        _, (_, _, attn), (slots_head, slots, mask_predictions) = student_output
         _, teacher_scene_logit = teacher_outputs
-        fg, fgN = fg_mask
-        dev = slots_head.device
-        teacher = teacher_scene_logit.detach().to(device=dev, dtype=torch.float32).contiguous()
-        fg = fg.to(device=dev, dtype=torch.float32).contiguous()       # k/256 masks: the reference's .half() is value-preserving
-        fgN = fgN.to(device=dev, dtype=torch.float32).contiguous()
-        target = target.to(device=dev, dtype=torch.int64).contiguous()
-        total, losses, match, logits = HeadMatchLossFn.apply(
-            slots_head, slots, mask_predictions, attn, teacher, target, fg, fgN, self.num_action_classes,
-            self.scene_loss_weight, self.mask_prediction_loss_weight, self.mask_distill_loss_weight, self.scene_criterion == "CE")
-        self.last_match = match
-        if self.sync_loss_dict:
-            vals = losses.tolist()
-            loss_dict = {k: vals[i] for i, k in enumerate(LOSS_NAMES)}
-        else:
-            loss_dict = {k: losses[i] for i, k in enumerate(LOSS_NAMES)}
-        return total, logits, loss_dict
+        teacher = teacher_scene_logit.detach().to(device=student_output[2][0].device, dtype=torch.float32).contiguous()
+        return _matching_loss(self, student_output, teacher, target, fg_mask, self.scene_loss_weight)

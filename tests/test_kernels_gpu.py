@@ -496,6 +496,22 @@ def test_head_match_loss(dtype, B, S, nb):
     assert sel[:, 1].tolist() == p[:, :, nb:].max(-1).values.argmax(1).tolist()
 
 
+def test_head_match_loss_refuses_rows_that_disagree():
+    """the kernels index every tensor from the dims alone: a teacher or `slots` with a row too few is a ValueError before anything is launched"""
+    o = ops()
+    B, S, C, nb, D, G, N, nh = 2, 2, 5, 3, 8, 4, 4, 1
+    Z, slots, maskp = rnd(B * S, C, seed=70), rnd(B * S, D, seed=71), torch.sigmoid(rnd(B * S, G, seed=72))
+    attn = torch.softmax(rnd(B * nh, S, N, seed=73), dim=1)
+    teacher, target = rnd(B, C - nb, seed=74), torch.tensor([0, 2], device=DEV)
+    fg, fgN = torch.full((B, G), 0.5, device=DEV), torch.full((B, N), 0.5, device=DEV)
+    before = o.counters()
+    with pytest.raises(ValueError):
+        o.head_match_loss_fwd(Z, slots, maskp, attn, teacher[:B - 1].contiguous(), target, fg, fgN, nb, 4000.0, 1.0, 1.0)
+    with pytest.raises(ValueError):
+        o.head_match_loss_fwd(Z, slots[:B * S - 1].contiguous(), maskp, attn, teacher, target, fg, fgN, nb, 4000.0, 1.0, 1.0)
+    assert o.counters() == before
+
+
 def test_adamw_matches_torch():
     o = ops()
     p = rnd(10007, seed=60); g = rnd(10007, seed=61)
