@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 169                # devias_version() of the library these prototypes describe
+ABI_VERSION = 170                # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -106,6 +106,7 @@ PROTOTYPES = {
     "devias_counters_reset": (None, []),
     "devias_set_option": (c_int, [c_char_p, c_int32]),
     "devias_get_option": (c_int, [c_char_p, POINTER(c_int32)]),
+    "devias_option_name": (c_char_p, [c_int32]),
     "devias_debug_mfma_probe": (c_int, [_P, _L, _I, _I, _P, _P, _P]),
     "devias_debug_mfma_probe_flops": (c_int64, [_I, _I]),
     "devias_debug_gemm_timer_arm": (c_int, [_I, _I, _I, _I, _I]),

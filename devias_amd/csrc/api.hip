@@ -12,7 +12,7 @@ int devias_set_error(int code, const char* fmt, ...) {
     return code;
 }
 
-extern "C" int devias_version(void) { return 169; }   // 169: launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM, DEVIAS_CNT_SLOTF_VALU, DEVIAS_CNT_SLOT; additive); 168: devias_head_match_loss_labels_fwd / _bwd (ground-truth scene labels; additive), DEVIAS_CNT_LOSS_LABELS; 167: devias_mhsa_*_flags (DEVIAS_ATTN_Q_PRESCALED), devias_block_args grew by WqkvS / qkv_biasS (recompile callers), option attn_qpre; 166: devias_block_args grew by the optional transposed weight copies W*T (recompile callers); 165: launch counters per dK / dV kernel form (DEVIAS_CNT_DKDV*, DEVIAS_CNT_MAX 24), option gemm_epi_spec (additive); 164: devias_mhsa_bwd uses its ws again (row statistics of the one-wave-per-SIMD dK / dV kernel), devias_mhsa_bwd_bias accepts dbv = NULL where devias_mhsa_bwd_bias_dv_from_do() says so; 163: devias_get_option, devias_gemm_release_queue_stream (additive); 162: devias_mhsa_bwd_bias (additive); 161: devias_mhsa_fwd_dropout / _bwd_dropout (additive); 160: devias_loss_dims.scene_ce (struct grew); 110: multi-tensor optimizer entry points, 120: devias_fame_*, 130: counters + options, 140: stream-K GEMM (args struct grew), 150: fused regions, roctx ranges
+extern "C" int devias_version(void) { return 170; }   // 170: devias_option_name, option slot_mfma (additive); 169: launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM, DEVIAS_CNT_SLOTF_VALU, DEVIAS_CNT_SLOT; additive); 168: devias_head_match_loss_labels_fwd / _bwd (ground-truth scene labels; additive), DEVIAS_CNT_LOSS_LABELS; 167: devias_mhsa_*_flags (DEVIAS_ATTN_Q_PRESCALED), devias_block_args grew by WqkvS / qkv_biasS (recompile callers), option attn_qpre; 166: devias_block_args grew by the optional transposed weight copies W*T (recompile callers); 165: launch counters per dK / dV kernel form (DEVIAS_CNT_DKDV*, DEVIAS_CNT_MAX 24), option gemm_epi_spec (additive); 164: devias_mhsa_bwd uses its ws again (row statistics of the one-wave-per-SIMD dK / dV kernel), devias_mhsa_bwd_bias accepts dbv = NULL where devias_mhsa_bwd_bias_dv_from_do() says so; 163: devias_get_option, devias_gemm_release_queue_stream (additive); 162: devias_mhsa_bwd_bias (additive); 161: devias_mhsa_fwd_dropout / _bwd_dropout (additive); 160: devias_loss_dims.scene_ce (struct grew); 110: multi-tensor optimizer entry points, 120: devias_fame_*, 130: counters + options, 140: stream-K GEMM (args struct grew), 150: fused regions, roctx ranges
 
 // ---- launch counters: which kernel family served a call (tests assert that the measured kernels are the ones under test) ----
 #include <atomic>
@@ -21,24 +21,48 @@ void devias_count(int id) { if (id >= 0 && id < DEVIAS_CNT_MAX) g_cnt[id].fetch_
 extern "C" int64_t devias_counter(int32_t id) { return (id >= 0 && id < DEVIAS_CNT_MAX) ? g_cnt[id].load(std::memory_order_relaxed) : -1; }
 extern "C" void devias_counters_reset(void) { for (int i = 0; i < DEVIAS_CNT_MAX; ++i) g_cnt[i].store(0, std::memory_order_relaxed); }
 
+// ---- process-wide options: the table of common.h, its values read from the environment ONCE, changeable at run time (tests, A/B tools) ----
+#include <stdlib.h>
+namespace {
+struct OptionRow { const char* name; const char* env; int dflt; };
+const OptionRow g_option_rows[OPT_COUNT] = {
+#define DEVIAS_OPTION_ROW(id, name, env, dflt) {name, env, dflt},
+    DEVIAS_OPTION_TABLE(DEVIAS_OPTION_ROW)
+#undef DEVIAS_OPTION_ROW
+};
+struct OptionValues {
+    int v[OPT_COUNT];
+    OptionValues() {
+        for (int i = 0; i < OPT_COUNT; ++i) { const char* e = getenv(g_option_rows[i].env); v[i] = e ? atoi(e) : g_option_rows[i].dflt; }
+    }
+};
+int option_index(const char* name) {
+    for (int i = 0; i < OPT_COUNT; ++i) if (!strcmp(name, g_option_rows[i].name)) return i;
+    return -1;
+}
+}  // namespace
+int* devias_options() { static OptionValues o; return o.v; }
+
+extern "C" const char* devias_option_name(int32_t index) { return (index >= 0 && index < OPT_COUNT) ? g_option_rows[index].name : nullptr; }
+
 extern "C" int devias_set_option(const char* name, int32_t value) {
     if (!name) return devias_set_error(DEVIAS_EINVAL, "devias_set_option: null name");
-    if (devias_gemm_set_option(name, value) || devias_attn_set_option(name, value)) return DEVIAS_OK;
-    if (!strcmp(name, "regions_defer")) { devias_defer_enabled() = value; return DEVIAS_OK; }
-    return devias_set_error(DEVIAS_EINVAL, "devias_set_option: unknown option '%s'", name);
+    const int i = option_index(name);
+    if (i < 0) return devias_set_error(DEVIAS_EINVAL, "devias_set_option: unknown option '%s'", name);
+    devias_options()[i] = (i == OPT_GEMM_RESERVE_CUS && value < 0) ? 0 : value;      // a reserve is a count of CUs
+    return DEVIAS_OK;
 }
 
 extern "C" int devias_get_option(const char* name, int32_t* value) {
     if (!name || !value) return devias_set_error(DEVIAS_EINVAL, "devias_get_option: null argument");
-    int v = 0;
-    if (devias_gemm_get_option(name, &v) || devias_attn_get_option(name, &v)) { *value = v; return DEVIAS_OK; }
-    if (!strcmp(name, "regions_defer")) { *value = devias_defer_enabled(); return DEVIAS_OK; }
-    return devias_set_error(DEVIAS_EINVAL, "devias_get_option: unknown option '%s'", name);
+    const int i = option_index(name);
+    if (i < 0) return devias_set_error(DEVIAS_EINVAL, "devias_get_option: unknown option '%s'", name);
+    *value = devias_options()[i];
+    return DEVIAS_OK;
 }
 
 extern "C" const char* devias_last_error(void) { return g_err; }
 DeviasDeferList*& devias_defer_slot() { static thread_local DeviasDeferList* slot = nullptr; return slot; }
-int& devias_defer_enabled() { static int on = [] { const char* e = getenv("DEVIAS_REGIONS_DEFER"); return e ? atoi(e) : 1; }(); return on; }
 
 extern "C" int devias_device_info(int device, int64_t* out5) {
     if (!out5) return devias_set_error(DEVIAS_EINVAL, "devias_device_info: null output");
@@ -92,7 +116,6 @@ extern "C" void devias_shutdown(void) { devias_counters_reset(); }
 
 // ---- ROCTX ranges (roctx_shim.h) ------------------------------------------------------------------------------------------------------------
 #include "roctx_shim.h"
-#include <stdlib.h>
 typedef int (*roctx_push_fn)(const char*);
 typedef int (*roctx_pop_fn)(void);
 static roctx_push_fn g_roctx_push = nullptr;

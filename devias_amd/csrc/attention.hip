@@ -16,8 +16,6 @@
 //
 // qkv layout is [B, N, 3, H, 64] exactly as produced by the fused QKV GEMM; o / d_o are [B, N, H*64].
 #include "common.h"
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 namespace {
@@ -1149,44 +1147,9 @@ __global__ __launch_bounds__(128) void mhsa_bwd_dkdv_f32_kernel(const float* __r
 
 }  // namespace
 
-// process-wide options, read from the environment once; devias_set_option("attn_cfg" | "attn_xcd", v) changes them at run time
-namespace {
-struct AttnKnobs { int cfg, xcd, bias_fused, dkdv, qpre; };
-AttnKnobs& attn_knobs() {
-    static AttnKnobs k = [] {
-        AttnKnobs x;
-        const char* e = getenv("DEVIAS_ATTN_CFG"); x.cfg = e ? atoi(e) : 0;
-        e = getenv("DEVIAS_ATTN_XCD"); x.xcd = e ? atoi(e) : 1;
-        e = getenv("DEVIAS_ATTN_BIAS_FUSED"); x.bias_fused = e ? atoi(e) : 1;
-        e = getenv("DEVIAS_ATTN_DKDV"); x.dkdv = e ? atoi(e) : 1;
-        e = getenv("DEVIAS_ATTN_QPRE"); x.qpre = e ? atoi(e) : 1;
-        return x;
-    }();
-    return k;
-}
-}  // namespace
-static int* attn_option_slot(const char* name) {
-    if (!strcmp(name, "attn_cfg")) return &attn_knobs().cfg;
-    if (!strcmp(name, "attn_xcd")) return &attn_knobs().xcd;
-    if (!strcmp(name, "attn_qpre")) return &attn_knobs().qpre;              // 1 (default): a HOST-side policy read by devias_amd/modeling_slot.py -- bf16 encoder blocks without attention dropout run their qkv GEMM on a q-scaled weight copy and the attention kernels with DEVIAS_ATTN_Q_PRESCALED; 0: q unscaled, every kernel applies scale * log2 e itself (A/B aid).  The library itself follows the caller's flags / devias_block_args.WqkvS
-    if (!strcmp(name, "attn_dkdv")) return &attn_knobs().dkdv;              // 1 (default): dK / dV by the one-wave-per-SIMD kernel (attn_bwd1w.hip), one workgroup per 256-key block; 2: the same kernel, one persistent workgroup per CU (the kernel alone -2 %, the step +-0: DESIGN.md section 5 round 5); 0: the two-waves-per-SIMD kernel
-    if (!strcmp(name, "attn_bias_fused")) return &attn_knobs().bias_fused;      // 0: devias_mhsa_bwd_bias takes the bias gradients by column-sum passes in bf16 too (A/B aid)
-    return nullptr;
-}
-int devias_attn_set_option(const char* name, int value) {
-    int* slot = attn_option_slot(name);
-    if (slot) *slot = value;
-    return slot != nullptr;
-}
-int devias_attn_get_option(const char* name, int* value) {
-    const int* slot = attn_option_slot(name);
-    if (slot) *value = *slot;
-    return slot != nullptr;
-}
-
 // bit 0: XCD-aware linear grid (needs B*H % 8 == 0); bits 16..: B.  Option attn_xcd = 0 restores the plain 3-D grid.
 static int attn_xcd_flag(int B, int H) {
-    return (B << 16) | ((attn_knobs().xcd && ((B * H) % 8 == 0)) ? 1 : 0);
+    return (B << 16) | ((devias_options()[OPT_ATTN_XCD] && ((B * H) % 8 == 0)) ? 1 : 0);
 }
 
 // keep >= 1: no dropout.  thresh = floor(keep * 2^32) (at most 2^32 - 1), seed = (s1 << 32) | s0
@@ -1210,7 +1173,7 @@ static int mhsa_fwd_impl(const void* qkv, void* o, float* lse, int32_t B, int32_
     DEVIAS_REQUIRE((flags & ~DEVIAS_ATTN_Q_PRESCALED) == 0 && (flags == 0 || dtype == DEVIAS_BF16), "devias_mhsa_fwd: bad flags %d (DEVIAS_ATTN_Q_PRESCALED: bf16 only)", flags);
     if (dtype == DEVIAS_BF16)
         {
-        const int cfg = attn_knobs().cfg;
+        const int cfg = devias_options()[OPT_ATTN_CFG];
         const int xcd = attn_xcd_flag(B, H) | ((flags & DEVIAS_ATTN_Q_PRESCALED) ? ATTN_QPRE : 0);
         devias_count(DEVIAS_CNT_MHSA_FWD_BF16);
         if (xcd & ATTN_QPRE) devias_count(DEVIAS_CNT_MHSA_QPRE);
@@ -1257,7 +1220,7 @@ int devias_attn_dkdv1w_launch(const void* qkv, const void* d_o, const float* sta
 // against 337 per layer: tools/exp/attn_bwd1w_dq.hip.txt, profiles/r5_dkdv1w_development.txt.  One wave overlaps its own MFMAs and vector instructions only inside
 // the MFMA's shadow; three waves overlap each other's.  The dK / dV kernel wins as one wave because its 128 accumulator registers leave no room for a second.)
 // true = devias_mhsa_bwd* runs the one-wave-per-SIMD dK / dV kernel for this call (bf16, no attention dropout, option attn_dkdv != 0, room for the statistics)
-static inline bool attn_use_dkdv1w(int dtype, float keep) { return dtype == DEVIAS_BF16 && !(keep < 1.0f) && attn_knobs().dkdv != 0; }
+static inline bool attn_use_dkdv1w(int dtype, float keep) { return dtype == DEVIAS_BF16 && !(keep < 1.0f) && devias_options()[OPT_ATTN_DKDV] != 0; }
 
 
 static int mhsa_bwd_impl(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, void* dqkv,
@@ -1271,7 +1234,8 @@ static int mhsa_bwd_impl(const void* qkv, const void* o, const void* d_o, const 
     DEVIAS_REQUIRE(H <= 65535 && B <= 65535, "devias_mhsa_bwd: H and B must be <= 65535");
     DEVIAS_REQUIRE((flags & ~DEVIAS_ATTN_Q_PRESCALED) == 0 && (flags == 0 || dtype == DEVIAS_BF16), "devias_mhsa_bwd: bad flags %d (DEVIAS_ATTN_Q_PRESCALED: bf16 only)", flags);
     if (dtype == DEVIAS_BF16) {
-        const int cfg = attn_knobs().cfg;
+        const int* opt = devias_options();
+        const int cfg = opt[OPT_ATTN_CFG];
         const int xcd = attn_xcd_flag(B, H) | ((flags & DEVIAS_ATTN_Q_PRESCALED) ? ATTN_QPRE : 0);
         devias_count(DEVIAS_CNT_MHSA_BWD_BF16);
         if (xcd & ATTN_QPRE) devias_count(DEVIAS_CNT_MHSA_QPRE);
@@ -1291,7 +1255,8 @@ static int mhsa_bwd_impl(const void* qkv, const void* o, const void* d_o, const 
 #undef DQ_ARGS
         DEVIAS_CHECK_LAUNCH("devias_mhsa_bwd(dq)");
         if (w1) {
-            const int rc = devias_attn_dkdv1w_launch(qkv, d_o, stat, dqkv, B, N, npad, H, scale, xcd, attn_knobs().dkdv == 2, st);
+            // attn_dkdv = 2: one persistent workgroup per CU instead of one per 256-key block (the kernel alone -2 %, the step +-0: DESIGN.md section 5 round 5)
+            const int rc = devias_attn_dkdv1w_launch(qkv, d_o, stat, dqkv, B, N, npad, H, scale, xcd, opt[OPT_ATTN_DKDV] == 2, st);
             if (rc != DEVIAS_OK) return rc;
         } else {
             devias_count(DEVIAS_CNT_DKDV2W);
@@ -1372,7 +1337,7 @@ static int mhsa_bwd_bias_impl(const void* qkv, const void* o, const void* d_o, c
         return devias_colsum(d_o, dtype, B * N, D, D, dbv, 0.f, ws_v, stream);
     }
     DEVIAS_REQUIRE(dbv, "devias_mhsa_bwd_bias: dbv may be NULL only where devias_mhsa_bwd_bias_dv_from_do() says so");
-    if (dtype == DEVIAS_BF16 && attn_knobs().bias_fused) {
+    if (dtype == DEVIAS_BF16 && devias_options()[OPT_ATTN_BIAS_FUSED]) {
         const int rc = mhsa_bwd_impl(qkv, o, d_o, lse, delta, dqkv, B, N, H, scale, dtype, keep, seed, stream, ws_q, ws_v, nullptr, flags);
         if (rc != DEVIAS_OK) return rc;
         const int rows = B * cdiv(N, 128);

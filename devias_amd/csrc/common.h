@@ -18,13 +18,43 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 #define WAVE 64
 
 int devias_set_error(int code, const char* fmt, ...);
-int devias_policy_gemm_wt(void);                            // option gemm_wt (gemm.hip): the fused encoder block may run its dgrad GEMMs on transposed weight copies
 void devias_count(int id);                                  // launch counters (api.hip): DEVIAS_CNT_* of include/devias_amd.h
-int devias_gemm_set_option(const char* name, int value);    // per-module option handlers behind devias_set_option: 1 = name known
-int devias_attn_set_option(const char* name, int value);
-int devias_gemm_get_option(const char* name, int* value);    // ... and behind devias_get_option
-int devias_attn_get_option(const char* name, int* value);
 extern "C" int32_t devias_policy_gemm_cus(void);             // gemm.hip: CUs the big-tile grids count on (device CUs - option gemm_reserve_cus)
+
+// ---- process-wide options ----------------------------------------------------------------------------------------------------------------
+// ONE row per option: (id, name for devias_set_option / devias_get_option, environment variable read once at first use, default).  What each value
+// selects is documented per option in include/devias_amd.h; the measurements behind a default stand at the dispatch branch that reads it.
+#define DEVIAS_OPTION_TABLE(X)                                              \
+    X(GEMM_EPI,         "gemm_epi",         "DEVIAS_GEMM_EPI",          1)  \
+    X(GEMM256,          "gemm256",          "DEVIAS_GEMM256",           1)  \
+    X(GEMM_SS,          "gemm_ss",          "DEVIAS_GEMM_SS",          -1)  \
+    X(GEMM_GROUPM,      "gemm_groupm",      "DEVIAS_GEMM_GROUPM",       0)  \
+    X(GEMM_PERSISTENT,  "gemm_persistent",  "DEVIAS_GEMM_PERSIST",      1)  \
+    X(GEMM_DEBUG,       "gemm_debug",       "DEVIAS_GEMM_DEBUG",        0)  \
+    X(GEMM_EPI_SPEC,    "gemm_epi_spec",    "DEVIAS_GEMM_EPI_SPEC",     1)  \
+    X(GEMM_WT,          "gemm_wt",          "DEVIAS_GEMM_WT",           1)  \
+    X(GEMM_AUX_NT,      "gemm_aux_nt",      "DEVIAS_GEMM_AUX_NT",       5)  \
+    X(GEMM_SMALLM,      "gemm_smallm",      "DEVIAS_GEMM_SMALLM",       1)  \
+    X(GEMM_TAIL_SPLIT,  "gemm_tail_split",  "DEVIAS_GEMM_TAIL_SPLIT",   3)  \
+    X(GEMM_W4,          "gemm_w4",          "DEVIAS_GEMM_W4",          -1)  \
+    X(GEMM_SPLITK_XCD,  "gemm_splitk_xcd",  "DEVIAS_GEMM_SPLITK_XCD",   1)  \
+    X(GEMM_DYNAMIC,     "gemm_dynamic",     "DEVIAS_GEMM_DYNAMIC",     -1)  \
+    X(GEMM_CONCURRENT,  "gemm_concurrent",  "DEVIAS_GEMM_CONCURRENT",   0)  \
+    X(GEMM_RESERVE_CUS, "gemm_reserve_cus", "DEVIAS_GEMM_RESERVE_CUS",  0)  \
+    X(ATTN_CFG,         "attn_cfg",         "DEVIAS_ATTN_CFG",          0)  \
+    X(ATTN_XCD,         "attn_xcd",         "DEVIAS_ATTN_XCD",          1)  \
+    X(ATTN_BIAS_FUSED,  "attn_bias_fused",  "DEVIAS_ATTN_BIAS_FUSED",   1)  \
+    X(ATTN_DKDV,        "attn_dkdv",        "DEVIAS_ATTN_DKDV",         1)  \
+    X(ATTN_QPRE,        "attn_qpre",        "DEVIAS_ATTN_QPRE",         1)  \
+    X(REGIONS_DEFER,    "regions_defer",    "DEVIAS_REGIONS_DEFER",     1)  \
+    X(SLOT_MFMA,        "slot_mfma",        "DEVIAS_SLOT_MFMA",         1)
+enum DeviasOption {
+#define DEVIAS_OPTION_ID(id, name, env, dflt) OPT_##id,
+    DEVIAS_OPTION_TABLE(DEVIAS_OPTION_ID)
+#undef DEVIAS_OPTION_ID
+    OPT_COUNT
+};
+int* devias_options();      // api.hip: the values, indexed by OPT_*; a host function fetches the table once per call
 
 #define DEVIAS_CHECK_LAUNCH(name)                                                              \
     do {                                                                                       \
@@ -59,7 +89,6 @@ static inline int devias_device_cus() {
 struct DeviasReduceJob { const float* part; int nparts; int stride; int n; float* out; float beta; };
 struct DeviasDeferList { enum { MAX = 16 }; DeviasReduceJob jobs[MAX]; int n; };
 DeviasDeferList*& devias_defer_slot();                            // api.hip: thread-local; non-null only while a region is collecting
-int& devias_defer_enabled();                                      // api.hip: option "regions_defer" / DEVIAS_REGIONS_DEFER (1, default; 0 = every second stage its own launch)
 int devias_flush_deferred(DeviasDeferList* l, hipStream_t st);    // elementwise.hip
 int64_t devias_layernorm_bwd_parts_count(int M);                  // layernorm.hip: partial rows that devias_layernorm_bwd_parts writes for M rows ([count][3][D] floats)
 int devias_layernorm_bwd_parts(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres, void* dx, float* part,
@@ -69,7 +98,7 @@ int devias_row_scale_colsum(const void* x, const float* scale, int rps, void* y,
 // true = the `count` second stages described by `j` were taken over by the collecting region (the caller must NOT launch them)
 static inline bool devias_defer(const DeviasReduceJob* j, int count) {
     DeviasDeferList* l = devias_defer_slot();
-    if (!l || !devias_defer_enabled() || l->n + count > DeviasDeferList::MAX) return false;
+    if (!l || !devias_options()[OPT_REGIONS_DEFER] || l->n + count > DeviasDeferList::MAX) return false;
     for (int i = 0; i < count; ++i) l->jobs[l->n++] = j[i];
     return true;
 }

@@ -12,8 +12,6 @@
 #include "common.h"
 #include <mutex>
 #include <utility>
-#include <stdlib.h>
-#include <string.h>
 #include <atomic>
 
 namespace {
@@ -2149,64 +2147,6 @@ extern "C" int64_t devias_gemm_workspace_bytes(int32_t M, int32_t N, int32_t spl
     return split_k > 1 ? (int64_t)split_k * M * N * 4 : 0;
 }
 
-// ---- process-wide options: read from the environment ONCE, changeable at run time through devias_set_option (tests, A/B tools) --------
-namespace {
-struct GemmKnobs {
-    int epi_swap;      // "gemm_epi"        DEVIAS_GEMM_EPI      1 = register-transposed epilogue (default), 0 = LDS-staged
-    int use256;        // "gemm256"         DEVIAS_GEMM256       0 disables the 256x256 kernels
-    int use_ss;        // "gemm_ss"         DEVIAS_GEMM_SS       -1 = measured policy, 0 = never, 1 = prefer the single-stage 256x128 kernel for k-strided layouts
-    int group_m;       // "gemm_groupm"     DEVIAS_GEMM_GROUPM   0 = measured policy, > 0 forces the rasterisation group height
-    int persistent;    // "gemm_persistent" DEVIAS_GEMM_PERSIST  != 0: persistent 256x256 kernel where it applies (default), 0 = one tile per workgroup
-    int debug;         // "gemm_debug"      DEVIAS_GEMM_DEBUG    ablation bits; only honoured by a -DDEVIAS_GEMM_DEBUG build
-    int epi_spec;      // "gemm_epi_spec"   DEVIAS_GEMM_EPI_SPEC 1 (default): the eight-wave persistent kernel runs the instantiation whose epilogue switches are compile-time facts where one exists (same bits); 0: always the generic form (A/B aid)
-    int wt;            // "gemm_wt"         DEVIAS_GEMM_WT       1 (default): the encoder block's backward runs its dgrad GEMMs on the caller's transposed weight copies (devias_block_args.W*T) where given; 0: reads the weights k-strided (A/B aid; same bits)
-    int aux_nt;        // "gemm_aux_nt"     DEVIAS_GEMM_AUX_NT   5 (default): bit 0: the persistent kernels store the saved pre-activation of a GELU epilogue non-temporally -- nobody reads it before the backward --, bit 2: that launch's first output too (fc1; together -0.4 ... -0.5 ms per step, in-process A/B)
-    int smallm;        // "gemm_smallm"     DEVIAS_GEMM_SMALLM   1 (default): bf16 products with M <= 128 and B k-contiguous run on gemm_smallm_kernel (one launch, no split-K), a workgroup per 16-row tile where there are few column groups; 2: one workgroup per column group always (A/B aid)
-    int tail_split;    // "gemm_tail_split" DEVIAS_GEMM_TAIL_SPLIT  eight-wave persistent kernel: last partial round's tiles as 128-row halves on two workgroups (1), whose idle waves
-                       //                                        also skip the LDS-DMA of the A rows nobody multiplies (2); 3 (default) / 4: up to thirds / quarters where
-                       //                                        the launch allows (static tile lists, no column sums, B k-contiguous: else halves); 0 = whole tiles.  Every value: same bits
-    int w4;            // "gemm_w4"         DEVIAS_GEMM_W4       mask of the forms the four-wave persistent kernel (gemm256w_kernel) serves (see devias_gemm;
-                       //                                        15 = all four; -1, default: the measured policy -- none since round 6, all four where K >= 1024 and N >= 1024 before)
-    int splitk_xcd;    // "gemm_splitk_xcd" DEVIAS_GEMM_SPLITK_XCD 1 (default): split-K launches of the 256 x 256 kernel (the weight gradients) order their (slab, tile) pairs XCD-major; 0: (tile, slab) grid
-    int dynamic;       // "gemm_dynamic"    DEVIAS_GEMM_DYNAMIC  1: the persistent kernel's workgroups pull their tiles from per-XCD queues at run time (robust to CUs
-                       //                                        held or slowed by a concurrent kernel: -2.5 ms per step with 16 CUs held during backward, profiles/
-                       //                                        r4_cu_hog.txt); 0: the static per-workgroup tile lists (0.3 ms per step faster when the GPU is the
-                       //                                        step's alone); -1 (default): queues exactly when the host has announced concurrent kernels
-    int concurrent;    // "gemm_concurrent" DEVIAS_GEMM_CONCURRENT  the host runs other kernels beside the step's (devias_amd.parallel.GradSync sets it when the
-                       //                                        gradient all-reduce runs on its side stream, bench.py --cu-hog too); default 0
-    int reserve;       // "gemm_reserve_cus" DEVIAS_GEMM_RESERVE_CUS  the persistent grids leave this many CUs free (default 0).  Their static tile
-                       //                                        lists assume one resident workgroup per CU of the grid: with K CUs held by another kernel
-                       //                                        (RCCL during backward at N > 1) the K workgroups that find no CU run AFTER the others --
-                       //                                        a doubled tail, measured +17 % on the step with 8-32 CUs held (bench.py --cu-hog)
-    int ncu;
-};
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-GemmKnobs& knobs() {
-    static GemmKnobs k = [] {
-        GemmKnobs x;
-        x.epi_swap = env_int("DEVIAS_GEMM_EPI", 1);
-        x.use256 = env_int("DEVIAS_GEMM256", 1);
-        x.use_ss = env_int("DEVIAS_GEMM_SS", -1);
-        x.group_m = env_int("DEVIAS_GEMM_GROUPM", 0);
-        x.persistent = env_int("DEVIAS_GEMM_PERSIST", 1);
-        x.debug = env_int("DEVIAS_GEMM_DEBUG", 0);
-        x.reserve = env_int("DEVIAS_GEMM_RESERVE_CUS", 0);
-        x.splitk_xcd = env_int("DEVIAS_GEMM_SPLITK_XCD", 1);
-        x.dynamic = env_int("DEVIAS_GEMM_DYNAMIC", -1);
-        x.concurrent = env_int("DEVIAS_GEMM_CONCURRENT", 0);
-        x.w4 = env_int("DEVIAS_GEMM_W4", -1);
-        x.tail_split = env_int("DEVIAS_GEMM_TAIL_SPLIT", 3);
-        x.smallm = env_int("DEVIAS_GEMM_SMALLM", 1);
-        x.epi_spec = env_int("DEVIAS_GEMM_EPI_SPEC", 1);
-        x.wt = env_int("DEVIAS_GEMM_WT", 1);
-        x.aux_nt = env_int("DEVIAS_GEMM_AUX_NT", 5);
-        x.ncu = 0;                                        // (unused: the CU count is the current device's at every call, devias_device_cus())
-        return x;
-    }();
-    return k;
-}
-}  // namespace
-
 // The tile-queue ring of the CURRENT device's copy of the code object, and this launch's place in it.  The ring's protocol (launch n zeroes the slot of
 // launch n + TQ_RING / 2) is only sound while the launches that use one ring are ordered among themselves: the ring therefore belongs to ONE stream per
 // device -- the first that launches a dynamic-queue GEMM on it -- and has its own launch counter.  A launch on any other stream of that device gets no slot
@@ -2249,47 +2189,12 @@ extern "C" int devias_gemm_release_queue_stream(void* stream) {
     return DEVIAS_OK;
 }
 
-int devias_policy_gemm_wt(void) { return knobs().wt; }
-
-// CUs the big-tile grids may count on: the device's, minus the reserve (option gemm_reserve_cus), in whole XCD rows
+// CUs the big-tile grids may count on: the device's, minus the reserve (option gemm_reserve_cus), in whole XCD rows.  The persistent kernels' static tile
+// lists assume one resident workgroup per CU of the grid: with K CUs held by another kernel (RCCL during backward at N > 1) the K workgroups that find no
+// CU run AFTER the others -- a doubled tail, measured +17 % on the step with 8-32 CUs held (bench.py --cu-hog)
 extern "C" int32_t devias_policy_gemm_cus(void) {
-    const GemmKnobs& k = knobs();
-    const int ncu = devias_device_cus();
-    return (ncu - k.reserve > 8 ? ncu - k.reserve : 8) & ~7;
-}
-
-// the option's storage, or nullptr for a name this file does not own (devias_set_option / devias_get_option, api.hip)
-static int* gemm_option_slot(const char* name) {
-    GemmKnobs& k = knobs();
-    if (!strcmp(name, "gemm_epi")) return &k.epi_swap;
-    if (!strcmp(name, "gemm256")) return &k.use256;
-    if (!strcmp(name, "gemm_ss")) return &k.use_ss;
-    if (!strcmp(name, "gemm_groupm")) return &k.group_m;
-    if (!strcmp(name, "gemm_persistent")) return &k.persistent;
-    if (!strcmp(name, "gemm_debug")) return &k.debug;
-    if (!strcmp(name, "gemm_w4")) return &k.w4;
-    if (!strcmp(name, "gemm_tail_split")) return &k.tail_split;
-    if (!strcmp(name, "gemm_smallm")) return &k.smallm;
-    if (!strcmp(name, "gemm_epi_spec")) return &k.epi_spec;
-    if (!strcmp(name, "gemm_wt")) return &k.wt;
-    if (!strcmp(name, "gemm_aux_nt")) return &k.aux_nt;
-    if (!strcmp(name, "gemm_reserve_cus")) return &k.reserve;
-    if (!strcmp(name, "gemm_splitk_xcd")) return &k.splitk_xcd;
-    if (!strcmp(name, "gemm_dynamic")) return &k.dynamic;
-    if (!strcmp(name, "gemm_concurrent")) return &k.concurrent;
-    return nullptr;
-}
-int devias_gemm_set_option(const char* name, int value) {
-    int* slot = gemm_option_slot(name);
-    if (!slot) return 0;
-    *slot = (!strcmp(name, "gemm_reserve_cus") && value < 0) ? 0 : value;
-    return 1;
-}
-int devias_gemm_get_option(const char* name, int* value) {
-    const int* slot = gemm_option_slot(name);
-    if (!slot) return 0;
-    *value = *slot;
-    return 1;
+    const int ncu = devias_device_cus(), reserve = devias_options()[OPT_GEMM_RESERVE_CUS];
+    return (ncu - reserve > 8 ? ncu - reserve : 8) & ~7;
 }
 
 // The eight-wave persistent kernel's instantiation for a call: operand layout, the rows its epilogue reads (SIDE), static lists or dynamic queues, and -- option
@@ -2327,7 +2232,7 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
     DEVIAS_REQUIRE(a->act >= 0 && a->act <= DEVIAS_ACT_DRELU, "devias_gemm: bad act %d", a->act);
     if (a->act == DEVIAS_ACT_DGELU || a->act == DEVIAS_ACT_DRELU)
         DEVIAS_REQUIRE(a->aux_in, "devias_gemm: act %d needs aux_in", a->act);
-    const GemmKnobs& kn = knobs();
+    const int* opt = devias_options();
     const int es = a->dtype == DEVIAS_BF16 ? 2 : 4;
     const int ch = 16 / es;
     GemmP p;
@@ -2371,18 +2276,18 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
     if (batch > 1)
         DEVIAS_REQUIRE(split == 1 && !a->colsum && !a->res && !a->aux_in && !a->aux_out && batch <= 65535,
                        "devias_gemm: batched launches support bias / activation epilogues only (no split-K, residual, aux, colsum)");
-    p.debug = kn.debug;
-    p.tail_split = kn.tail_split;
-    p.aux_nt = kn.aux_nt;
+    p.debug = opt[OPT_GEMM_DEBUG];
+    p.tail_split = opt[OPT_GEMM_TAIL_SPLIT];
+    p.aux_nt = opt[OPT_GEMM_AUX_NT];
     // C non-temporal too (bit 2) for the GELU launch with a second output: fc1 writes 2 x 308 MB per launch at B = 32, more than any cache keeps for its consumer, and written
     // through the XCDs' L2s they displace the operand panels (the fat tail of fc1's K loops, profiles/r6_gemm_pstamps.txt).  In-process A/B (profiles/r6_ab_inproc.txt): the second
     // output alone -0.03 ... -0.17 ms, BOTH -0.34 ... -0.41 ms on top (C alone +0.30); the same for qkv's output (+0.08) or dfc2's (+0.20, its consumers are the next two launches): no.
-    p.c_nt = ((kn.aux_nt & 4) && a->aux_out) ? 1 : 0;
-    p.epi_swap = kn.epi_swap;
+    p.c_nt = ((opt[OPT_GEMM_AUX_NT] & 4) && a->aux_out) ? 1 : 0;
+    p.epi_swap = opt[OPT_GEMM_EPI];
     p.tq = nullptr; p.tq_clear = nullptr; p.tq_nwhole[0] = p.tq_nwhole[1] = p.tq_items[0] = p.tq_items[1] = 0;
     // rasterisation (measured, tools/gemm_ablate.py): wide outputs (N >= 2048) gain 7-10 % from 8-row-tile groups (the
     // weight panel set of a group stays in the XCD's L2); narrow ones and the wgrad reductions are best n-fastest
-    p.group_m = kn.group_m > 0 ? kn.group_m : ((!a->trans_a && a->N >= 2048) ? 8 : 1);
+    p.group_m = opt[OPT_GEMM_GROUPM] > 0 ? opt[OPT_GEMM_GROUPM] : ((!a->trans_a && a->N >= 2048) ? 8 : 1);
 
     // 16 bytes per lane in the staged epilogue (8 bf16 / 2 x 4 fp32): leading dims % 8 and 16-byte aligned bases
     const bool v16 = vc && (a->N % 8 == 0) && (a->ldc % 8 == 0) && aligned16(a->C) && (!a->bias || aligned16(a->bias)) &&
@@ -2390,7 +2295,7 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
                      (!a->aux_in || ((a->ld_aux % 8 == 0) && aligned16(a->aux_in))) &&
                      (!a->aux_out || ((a->ld_aux % 8 == 0) && aligned16(a->aux_out))) && (split == 1 || aligned16(a->ws));
     p.vec16 = (v16 && a->dtype == DEVIAS_BF16) ? 1 : 0;
-    bool big = kn.use256 && a->dtype == DEVIAS_BF16 && vec && vc && (a->M % T2 == 0) && (a->N % T2 == 0) && (a->K % 64 == 0) &&
+    bool big = opt[OPT_GEMM256] && a->dtype == DEVIAS_BF16 && vec && vc && (a->M % T2 == 0) && (a->N % T2 == 0) && (a->K % 64 == 0) &&
                (p.k_per_split % 64 == 0);
     big = big && v16 && batch == 1;
     // Kernel choice, measured on MI355X at the ViT-B shapes (M = 50176; tools/gemm_block_shapes.py, tools/ab_bench.py):
@@ -2398,15 +2303,15 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
     //     (gemm256p_kernel) when there is more than one round of tiles, no split-K and a bf16 output (forward and dgrad GEMMs);
     //   * 256x128 single-stage kernel (2 workgroups/CU): N a multiple of 128 but not of 256;
     //   * 128x128 register-staged kernel: ragged / unaligned / fp32 shapes.
-    bool ss = kn.use_ss != 0 && a->dtype == DEVIAS_BF16 && vec && v16 && (a->M % SS_BM == 0) && (a->N % SS_BN == 0) && (a->K % 64 == 0) &&
+    bool ss = opt[OPT_GEMM_SS] != 0 && a->dtype == DEVIAS_BF16 && vec && v16 && (a->M % SS_BM == 0) && (a->N % SS_BN == 0) && (a->K % 64 == 0) &&
               (p.k_per_split % 64 == 0) && batch == 1 && !(a->trans_a && !a->trans_b);      // (A k-strided with B k-contiguous: no caller; that
                                                                                              //  instantiation spilled registers and was removed)
     if (ss && big) {
         const bool nt = !a->trans_a && !a->trans_b;
-        if (kn.use_ss < 0 || nt) ss = false;
+        if (opt[OPT_GEMM_SS] < 0 || nt) ss = false;
     }
     // small-M products (the aggregation block's and the head's B*S-row GEMMs): one launch, no split-K (gemm_smallm_kernel)
-    const bool smallm = kn.smallm && a->dtype == DEVIAS_BF16 && !a->trans_a && (!a->trans_b || kn.smallm == 1) && a->M <= 128 && batch == 1 && !p.c_f32 && !a->colsum && vec && vc &&
+    const bool smallm = opt[OPT_GEMM_SMALLM] && a->dtype == DEVIAS_BF16 && !a->trans_a && (!a->trans_b || opt[OPT_GEMM_SMALLM] == 1) && a->M <= 128 && batch == 1 && !p.c_f32 && !a->colsum && vec && vc &&
                         (a->N % 16 == 0) && (a->K % 128 == 0) && (a->lda % 8 == 0) && (a->ldb % 8 == 0) && (a->ldc % 4 == 0) && aligned8(a->C) &&
                         (!a->bias || aligned16(a->bias)) && (!a->res || (a->ldr % 4 == 0 && aligned8(a->res))) &&
                         (!a->aux_in || (a->ld_aux % 4 == 0 && aligned8(a->aux_in))) && (!a->aux_out || (a->ld_aux % 4 == 0 && aligned8(a->aux_out)));
@@ -2420,7 +2325,7 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
         // -0.13 ms with the split alone, -0.25 ms with twelve instead of four k-steps of loads in flight per wave (a wave's 24 k-steps are then two round trips to
         // memory instead of six) -- tools/ab_inproc.py gemm_smallm=2,1
         if (a->trans_b) { grid = dim3(a->N / 16, mt); hipLaunchKernelGGL((gemm_smallm_kernel<1, 12, true>), grid, block, 0, st, p); }      // W stored [K, N]: always a workgroup per row tile
-        else if (kn.smallm == 1 && mt > 1 && a->N / 16 < 128) { grid = dim3(a->N / 16, mt); hipLaunchKernelGGL((gemm_smallm_kernel<1, 12>), grid, block, 0, st, p); }
+        else if (opt[OPT_GEMM_SMALLM] == 1 && mt > 1 && a->N / 16 < 128) { grid = dim3(a->N / 16, mt); hipLaunchKernelGGL((gemm_smallm_kernel<1, 12>), grid, block, 0, st, p); }
         else
         if (mt <= 1) hipLaunchKernelGGL((gemm_smallm_kernel<1, 12>), grid, block, 0, st, p);
         else if (mt <= 2) hipLaunchKernelGGL((gemm_smallm_kernel<2>), grid, block, 0, st, p);
@@ -2451,7 +2356,9 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
         const int nt = p.tiles_m * p.tiles_n;
         // grid of the persistent forms: one workgroup per CU the policy counts on.  With the dynamic queues a reserve is pointless for THEM (a workgroup that
         // finds no CU pulls nothing): they launch on every CU, and gemm_reserve_cus then only sizes the weight-gradient split-K (one round of the CUs left)
-        const bool dyn = kn.dynamic > 0 || (kn.dynamic < 0 && kn.concurrent != 0);      // (round 6: queues only for fc1, or fc1 + dfc2 -- the launches whose tiles vary most --: -0.09 / -0.03 / -0.04 ms, noise)
+        // gemm_dynamic (profiles/r4_cu_hog.txt): the queues are robust to CUs held or slowed by a concurrent kernel, -2.5 ms per step with 16 CUs held during backward; the static
+        // lists are 0.3 ms per step faster when the GPU is the step's alone -- hence -1 (default): queues exactly when the host has announced concurrent kernels (gemm_concurrent)
+        const bool dyn = opt[OPT_GEMM_DYNAMIC] > 0 || (opt[OPT_GEMM_DYNAMIC] < 0 && opt[OPT_GEMM_CONCURRENT] != 0);      // (round 6: queues only for fc1, or fc1 + dfc2 -- the launches whose tiles vary most --: -0.09 / -0.03 / -0.04 ms, noise)
         const int gp = dyn ? (devias_device_cus() & ~7) : devias_policy_gemm_cus();
         // persistent form (more than one round of tiles, no split-K, bf16 output): measured per shape at M = 50176 (tools/gemm_block_shapes.py, same
         // box, one-tile-per-workgroup -> persistent): qkv 226 -> 204 us, fc1 278 -> 243, dfc2 + dGELU + colsum 415 -> 349, dfc2 plain 275 -> 248,
@@ -2477,18 +2384,18 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
         // Round 6, second session: with the eight-wave kernel's specialised epilogues, tail thirds and non-temporal fc1 outputs the measured policy (-1) is NONE -- ViT-L in
         // process (tools/ab_inproc.py --model vit_large gemm_w4=-1,0, the old policy "all four where K >= 1024 and N >= 1024" against none): -0.84 / -0.52 ms of 137.2; forms 1 / 2
         // alone against none +0.22 / -0.01 (profiles/r6_side_configs.txt).  Its N = 1024 shapes have 3.06 rounds of tiles and the four-wave kernel has no tail split.
-        const int w4_mask = kn.w4 >= 0 ? kn.w4 : 0;
-        const bool w4_ok = kn.persistent && !dyn && ((w4_mask >> w4_form) & 1) && pers_ok && !(!tb && side == 2) && nt > gp && a->K >= 128 &&      // (B k-contiguous + saved pre-activation -- dfc2 on a transposed weight copy -- has no four-wave form)
+        const int w4_mask = opt[OPT_GEMM_W4] >= 0 ? opt[OPT_GEMM_W4] : 0;
+        const bool w4_ok = opt[OPT_GEMM_PERSISTENT] && !dyn && ((w4_mask >> w4_form) & 1) && pers_ok && !(!tb && side == 2) && nt > gp && a->K >= 128 &&      // (B k-contiguous + saved pre-activation -- dfc2 on a transposed weight copy -- has no four-wave form)
                            (a->act == DEVIAS_ACT_NONE || a->act == DEVIAS_ACT_GELU || a->act == DEVIAS_ACT_DGELU || a->act == DEVIAS_ACT_DRELU);
         if (w4_ok) {
             dim3 grid(gp), block(NTW);
             PERS_LAUNCH(gemm256w_kernel);
             devias_count(DEVIAS_CNT_GEMM256P);
             devias_count(DEVIAS_CNT_GEMM256W);
-        } else if (kn.persistent && pers_ok && nt > gp) {
+        } else if (opt[OPT_GEMM_PERSISTENT] && pers_ok && nt > gp) {
             dim3 grid(gp);
             // the epilogue's switches of this call (EPI of epilogue_swap); -1 = the generic instantiation
-            const int epi = !kn.epi_spec ? -1 : (a->act | (a->bias ? EPI_BIAS : 0) | (a->aux_out ? EPI_AUX : 0) | (a->row_scale ? EPI_RS : 0) | (p.colsum_part ? EPI_CS : 0));
+            const int epi = !opt[OPT_GEMM_EPI_SPEC] ? -1 : (a->act | (a->bias ? EPI_BIAS : 0) | (a->aux_out ? EPI_AUX : 0) | (a->row_scale ? EPI_RS : 0) | (p.colsum_part ? EPI_CS : 0));
             // dynamic queue: every XCD queue has at least one (reserved) item per workgroup, at most 32 workgroups per XCD (one claim-mask word)
             unsigned int *tq = nullptr, *tq_clear = nullptr;
             if (!(dyn && a->K >= 128 && (gp >> 3) <= 32 && (nt >> 3) >= (gp >> 3) && tile_queue_slot(st, &tq, &tq_clear))) tq = nullptr;
@@ -2501,7 +2408,7 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
                 for (int v = 0; v < 2; ++v) {
                     const int cnt = (nt >> 3) + (v == 0 ? 1 : 0);
                     const int rfull = cnt / stride, rem = cnt - rfull * stride;
-                    const bool split = kn.tail_split != 0 && rfull >= 1 && rem > 0 && 2 * rem <= stride;
+                    const bool split = opt[OPT_GEMM_TAIL_SPLIT] != 0 && rfull >= 1 && rem > 0 && 2 * rem <= stride;
                     p.tq_nwhole[v] = split ? rfull * stride : cnt;
                     p.tq_items[v] = split ? rfull * stride + 2 * rem : cnt;
                 }
@@ -2513,7 +2420,7 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
             devias_count(DEVIAS_CNT_GEMM256P);
         } else {
             dim3 grid(nt, p.split_k), block(NT2);
-            if (p.split_k > 1 && kn.splitk_xcd) grid = dim3(8 * ((nt * p.split_k + 7) / 8));      // (slab, tile) pairs in XCD-major order (gemm256_kernel)
+            if (p.split_k > 1 && opt[OPT_GEMM_SPLITK_XCD]) grid = dim3(8 * ((nt * p.split_k + 7) / 8));      // (slab, tile) pairs in XCD-major order (gemm256_kernel)
             if (!ta && !tb) hipLaunchKernelGGL((gemm256_kernel<false, false, 1>), grid, block, 0, st, p);
             else if (!ta && tb) hipLaunchKernelGGL((gemm256_kernel<false, true>), grid, block, 0, st, p);
             else if (ta && tb) hipLaunchKernelGGL((gemm256_kernel<true, true>), grid, block, 0, st, p);

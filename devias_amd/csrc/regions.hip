@@ -210,7 +210,7 @@ extern "C" int devias_encoder_block_bwd(const devias_block_args* a, const void* 
     const BlockScratch t(scratch, B, N, D, H, hid, a->dtype);
     devias_range r("encoder_block_bwd");
     // transposed weight copies for the dgrad GEMMs: bf16 only (the fp32 kernels stage through registers: no gain), option gemm_wt
-    const bool wt = a->dtype == DEVIAS_BF16 && devias_policy_gemm_wt() != 0;
+    const bool wt = a->dtype == DEVIAS_BF16 && devias_options()[OPT_GEMM_WT] != 0;
     const void *WqkvT = wt ? a->WqkvT : nullptr, *WpT = wt ? a->WpT : nullptr, *W1T = wt ? a->W1T : nullptr, *W2T = wt ? a->W2T : nullptr;
     // The second stages of this region's partial reductions (two LayerNorm parameter reduces, the column-sum finals of db1 / db2 / dbp / dq_bias / dv_bias:
     // 5-7 launches of 6-12 us) run as ONE launch at the end: each producer gets a private partial area in the scratch arena (Ctx with that `ws`).

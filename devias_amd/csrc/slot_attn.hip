@@ -10,7 +10,6 @@
 //   * the K/V gradients of ALL weight-tied layers are produced by ONE pass at the end (devias_slot_attn_kv_grad) from
 //     the tiny per-layer ds / A / q / dO tensors, instead of a read-modify-write of the [B,N,2,h*dh] buffer per layer.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -900,8 +899,7 @@ extern "C" int64_t devias_slotf_workspace_bytes(int32_t B, int32_t S, int32_t N,
 
 // the matrix-core kernels: bf16, h * S <= 16 slot-head rows, S a power of two (softmax across S aligned adjacent lanes), D = 256 * {2, 3, 4}
 static bool slotm_ok(int B, int S, int h, int D, int dtype) {
-    static const int on = [] { const char* e = getenv("DEVIAS_SLOT_MFMA"); return e ? atoi(e) : 1; }();
-    return on && dtype == DEVIAS_BF16 && h * S <= 16 && (S == 1 || S == 2 || S == 4) && (D == 512 || D == 768 || D == 1024) && B <= 65535;
+    return devias_options()[OPT_SLOT_MFMA] && dtype == DEVIAS_BF16 && h * S <= 16 && (S == 1 || S == 2 || S == 4) && (D == 512 || D == 768 || D == 1024) && B <= 65535;
 }
 
 #define SLOTF_CHECKS(name)                                                                                                  \

@@ -2,6 +2,7 @@
 HIP stream; every bit of arithmetic happens in libdevias_amd.so.  No function here has a CPU or eager fallback."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Optional, Tuple
 
@@ -51,8 +52,6 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return ws
 
 
-
-
 def get_option(name: str) -> int:
     """devias_get_option: the current value of a process-wide option (to restore it after a temporary change)"""
     v = ctypes.c_int32(0)
@@ -61,8 +60,33 @@ def get_option(name: str) -> int:
 
 
 def set_option(name: str, value: int) -> None:
-    """devias_set_option: process-wide kernel-selection knobs (gemm_epi, gemm256, gemm_ss, gemm_groupm, gemm_persistent, attn_cfg, attn_xcd ...)"""
+    """devias_set_option: change a process-wide option (names, environment variables, defaults and meanings: the option block of include/devias_amd.h)"""
     _lib.check(_lib.load().devias_set_option(name.encode(), int(value)), "devias_set_option")
+
+
+def option_names() -> Tuple[str, ...]:
+    """devias_option_name: every option's name, in the library's table order"""
+    lib, names = _lib.load(), []
+    while (n := lib.devias_option_name(len(names))) is not None:
+        names.append(n.decode())
+    return tuple(names)
+
+
+@contextlib.contextmanager
+def options(**changes: int):
+    """Scope for option changes: snapshots EVERY option, applies `changes` (an unknown name raises before anything is changed) and on exit -- normal or by an
+    exception -- restores the whole snapshot, so set_option calls inside the block are undone too.  Nests."""
+    saved = {n: get_option(n) for n in option_names()}
+    unknown = sorted(set(changes) - set(saved))
+    if unknown:
+        raise ValueError(f"unknown option(s) {unknown}; the library has {sorted(saved)}")
+    try:
+        for n, v in changes.items():
+            set_option(n, v)
+        yield
+    finally:
+        for n, v in saved.items():
+            set_option(n, v)
 
 
 def release_gemm_queue_stream(stream=None) -> None:

@@ -123,18 +123,9 @@ def b32():
 
 @pytest.fixture
 def knobs():
-    """set_(name, value): a library option for this test only; every option touched is restored in `finally`"""
-    saved = {}
-
-    def set_(name, value):
-        if name not in saved:
-            saved[name] = ops.get_option(name)
-        ops.set_option(name, value)
-    try:
-        yield set_
-    finally:
-        for n, v in saved.items():
-            ops.set_option(n, v)
+    """set_(name, value): a library option for this test only; the scope restores every option when the test ends"""
+    with ops.options():
+        yield ops.set_option
 
 
 def test_fp32_mode_anchor_vs_oracle():
@@ -176,7 +167,7 @@ _ID = lambda d: "+".join(f"{k}={v}" for k, v in d.items())      # noqa: E731
 
 @pytest.mark.parametrize("opts", SAME_BITS, ids=_ID)
 def test_b32_option_gives_the_same_bits(b32, knobs, opts):
-    """Options of GemmKnobs (csrc/gemm.hip) and AttnKnobs (csrc/attention.hip) are each in SAME_BITS, BOUNDED, or excluded here:
+    """The gemm_* and attn_* options of the library's table (csrc/common.h) are each in SAME_BITS, BOUNDED, or excluded here:
     gemm_debug (ablation bits, honoured only by a -DDEVIAS_GEMM_DEBUG build) and gemm_concurrent alone (it only announces concurrent
     kernels to gemm_dynamic = -1, which then takes the dynamic queues: the gemm_dynamic = 1 case)."""
     for k, v in opts.items():

@@ -14,18 +14,14 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF, F32 = torch.bfloat16, torch.float32
 SCALE = 0.125
-OPTIONS = ("gemm_persistent", "gemm_epi", "gemm256", "gemm_ss", "gemm_w4", "gemm_tail_split", "gemm_smallm", "gemm_dynamic", "gemm_concurrent", "gemm_epi_spec",
-           "attn_dkdv", "attn_xcd")
 
 
 @pytest.fixture
 def options():
     """the ops module; every process-wide option is put back to the value it had"""
     from devias_amd import ops as o
-    saved = {k: o.get_option(k) for k in OPTIONS}
-    yield o
-    for k, v in saved.items():
-        o.set_option(k, v)
+    with o.options():
+        yield o
 
 
 def cdiv(a, b):

@@ -187,9 +187,7 @@ def test_layernorm_bwd_workspace_under_reserved_cus(reserve, dtype, M, D):
     from devias_amd import _lib
     o = ops()
     lib = _lib.load()
-    saved = o.get_option("gemm_reserve_cus")
-    try:
-        o.set_option("gemm_reserve_cus", reserve)
+    with o.options(gemm_reserve_cus=reserve):
         x = rnd(M, D, dtype=dtype, seed=20) * 2 + 0.5
         g, b = 1 + 0.1 * rnd(D, seed=21), 0.1 * rnd(D, seed=22)
         y, mean, rstd = o.layernorm_fwd(x, g, b, 1e-6)
@@ -216,8 +214,6 @@ def test_layernorm_bwd_workspace_under_reserved_cus(reserve, dtype, M, D):
         assert rel(dg, gr.grad) < (1e-4 if dtype == torch.float32 else 1e-3)
         assert rel(db, br.grad) < (1e-4 if dtype == torch.float32 else 1e-3)
         assert rel(cs, xr.grad.sum(0)) < (1e-4 if dtype == torch.float32 else 2e-2)
-    finally:
-        o.set_option("gemm_reserve_cus", saved)
 
 
 # ---------------------------------------------------------------------------------------------- attention
@@ -587,12 +583,10 @@ def test_fused_adamw_multi_equals_per_tensor_path_bitwise():
 # ------------------------------------------------------------------------------------------------ persistent GEMM
 @pytest.fixture
 def gemm_options():
-    """restores the process-wide kernel-selection options a test changes"""
+    """every process-wide option a test changes is back at its value from before the test when it ends"""
     o = ops()
-    yield o
-    for k, v in (("gemm_persistent", 1), ("gemm_epi", 1), ("gemm256", 1), ("gemm_ss", -1), ("gemm_w4", -1), ("gemm_tail_split", 3), ("gemm_smallm", 1),
-                 ("gemm_dynamic", -1), ("gemm_concurrent", 0), ("gemm_epi_spec", 1)):
-        o.set_option(k, v)
+    with o.options():
+        yield o
 
 
 def _persistent_serves(tb, epi):
@@ -816,8 +810,8 @@ def test_gemm_dynamic_queue_ring_belongs_to_one_stream(gemm_options):
 @pytest.fixture
 def attn_options():
     o = ops()
-    yield o
-    o.set_option("attn_xcd", 1)
+    with o.options():
+        yield o
 
 
 @pytest.mark.parametrize("B,N,H", [(2, 100, 3), (1, 1569, 1), (3, 130, 8)])
@@ -887,28 +881,25 @@ def test_mhsa_bwd_dkdv_forms_agree(B, N, H, attn_options):
     qkv = rnd(B * N, 3 * H * 64, dtype=torch.bfloat16, seed=70)
     d_o = rnd(B * N, H * 64, dtype=torch.bfloat16, seed=71)
     out, lse = o.mhsa_fwd(qkv, B, N, H, scale)
-    try:
-        res = {}
-        for form in (1, 2, 0, 2, 1):
-            o.set_option("attn_dkdv", form)
-            r = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale)
-            assert torch.isfinite(r.float()).all(), form
-            if form in res:
-                assert torch.equal(r, res[form]), form
-            res[form] = r
-        assert torch.equal(res[1], res[2])
-        a, b = res[1].float().reshape(B, N, 3, H, 64), res[0].float().reshape(B, N, 3, H, 64)
-        assert torch.equal(a[:, :, 0], b[:, :, 0])                       # dQ: the same kernel in every form
-        for w in (1, 2):
-            assert rel(a[:, :, w], b[:, :, w]) < 2.5e-2, w
-        if B * H * N * N <= 2e8:                                          # fp32 autograd of softmax(scale q k^T) v on the bf16-rounded inputs
-            x = qkv.float().view(B, N, 3, H, 64).detach().requires_grad_(True)
-            q, k, v = (x[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-            (torch.softmax((q * scale) @ k.transpose(-1, -2), dim=-1) @ v).permute(0, 2, 1, 3).reshape(B * N, H * 64).backward(d_o.float())
-            for w in range(3):
-                assert rel(a[:, :, w], x.grad[:, :, w]) < 3e-2, w
-    finally:
-        o.set_option("attn_dkdv", 1)
+    res = {}
+    for form in (1, 2, 0, 2, 1):
+        o.set_option("attn_dkdv", form)
+        r = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale)
+        assert torch.isfinite(r.float()).all(), form
+        if form in res:
+            assert torch.equal(r, res[form]), form
+        res[form] = r
+    assert torch.equal(res[1], res[2])
+    a, b = res[1].float().reshape(B, N, 3, H, 64), res[0].float().reshape(B, N, 3, H, 64)
+    assert torch.equal(a[:, :, 0], b[:, :, 0])                       # dQ: the same kernel in every form
+    for w in (1, 2):
+        assert rel(a[:, :, w], b[:, :, w]) < 2.5e-2, w
+    if B * H * N * N <= 2e8:                                          # fp32 autograd of softmax(scale q k^T) v on the bf16-rounded inputs
+        x = qkv.float().view(B, N, 3, H, 64).detach().requires_grad_(True)
+        q, k, v = (x[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        (torch.softmax((q * scale) @ k.transpose(-1, -2), dim=-1) @ v).permute(0, 2, 1, 3).reshape(B * N, H * 64).backward(d_o.float())
+        for w in range(3):
+            assert rel(a[:, :, w], x.grad[:, :, w]) < 3e-2, w
 
 
 @pytest.mark.parametrize("amp", [1.0, 2.5])
@@ -937,22 +928,19 @@ def test_mhsa_q_prescaled_scores_are_the_forwards(B, N, H, amp, attn_options):
     seen_pre = qkv_pre.float(); seen_pre[:, :D] /= c
     ref_plain, ref_pre = reference(qkv_plain), reference(seen_pre)
     err, rms = {}, {}
-    try:
-        for form in (1, 0):
-            o.set_option("attn_dkdv", form)
-            for name, qkv, flag, (ro, rg) in (("plain", qkv_plain, False, ref_plain), ("pre", qkv_pre, True, ref_pre)):
-                out, lse = o.mhsa_fwd(qkv, B, N, H, scale, q_prescaled=flag)
-                g = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale, q_prescaled=flag)
-                assert torch.equal(g, o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale, q_prescaled=flag)), (name, form)      # run to run
-                dbq = torch.zeros(D, device=DEV); dbv = torch.zeros(D, device=DEV)
-                gb = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale, bias_out=(dbq, dbv), q_prescaled=flag)                 # the _bias entry point: the same dqkv
-                assert torch.equal(g, gb), (name, form)
-                gf = g.float().view(B, N, 3, H, 64)
-                err[name, form] = [rel(out, ro)] + [rel(gf[:, :, w], rg[:, :, w]) for w in range(3)]
-                rms[name, form] = [float(((gf[:, :, w] - rg[:, :, w]).double().pow(2).mean() / rg[:, :, w].double().pow(2).mean()).sqrt()) for w in range(3)]
-                assert rel(dbq, rg[:, :, 0].sum((0, 1)).reshape(-1)) < 2e-2, (name, form)
-    finally:
-        o.set_option("attn_dkdv", 1)
+    for form in (1, 0):
+        o.set_option("attn_dkdv", form)
+        for name, qkv, flag, (ro, rg) in (("plain", qkv_plain, False, ref_plain), ("pre", qkv_pre, True, ref_pre)):
+            out, lse = o.mhsa_fwd(qkv, B, N, H, scale, q_prescaled=flag)
+            g = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale, q_prescaled=flag)
+            assert torch.equal(g, o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale, q_prescaled=flag)), (name, form)      # run to run
+            dbq = torch.zeros(D, device=DEV); dbv = torch.zeros(D, device=DEV)
+            gb = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale, bias_out=(dbq, dbv), q_prescaled=flag)                 # the _bias entry point: the same dqkv
+            assert torch.equal(g, gb), (name, form)
+            gf = g.float().view(B, N, 3, H, 64)
+            err[name, form] = [rel(out, ro)] + [rel(gf[:, :, w], rg[:, :, w]) for w in range(3)]
+            rms[name, form] = [float(((gf[:, :, w] - rg[:, :, w]).double().pow(2).mean() / rg[:, :, w].double().pow(2).mean()).sqrt()) for w in range(3)]
+            assert rel(dbq, rg[:, :, 0].sum((0, 1)).reshape(-1)) < 2e-2, (name, form)
     for key, e in err.items():
         if key[0] == "pre":                      # measured: out <= 4.1e-3, gradients <= 7.2e-3 at either amplitude
             assert e[0] < 8e-3 and max(e[1:]) < 1.5e-2, (key, e)
@@ -1115,7 +1103,6 @@ def test_gemm_small_m_kernel(M, N, K, epi, gemm_options):
             torch.cuda.synchronize()
             assert o.counters()["gemm_smallm"] == (1 if mode == 1 and served else 0), (mode, o.counters())
             outs[("t", mode)] = (ct, kw3.get("aux_out"))
-    o.set_option("gemm_smallm", 1)
     c, aux = outs[1]
     assert rel(c.float(), ref) < TOL[torch.bfloat16]
     assert rel(c.float(), outs[0][0].float()) < TOL[torch.bfloat16]
@@ -1129,3 +1116,30 @@ def test_gemm_small_m_kernel(M, N, K, epi, gemm_options):
         if aux is not None:
             assert torch.equal(auxt, aux)
     assert rel(ct.float(), ref) < TOL[torch.bfloat16] and rel(ct.float(), outs[("t", 0)][0].float()) < TOL[torch.bfloat16]
+
+
+def test_options_scope_selects_and_restores_the_gemm_kernel():
+    """ops.options around a real launch: inside the scope the split-K path serves the product, after it -- left normally or by an exception -- the small-M kernel
+    does again; both within the bf16 tolerance of the fp32 product (the smallest shape that reaches the choice)"""
+    o = ops()
+    M, N, K = 64, 768, 256
+    A = rnd(M, K, dtype=torch.bfloat16, seed=41)
+    W = rnd(N, K, dtype=torch.bfloat16, scale=0.1, seed=42)
+    ref = A.float() @ W.float().t()
+
+    def call():
+        o.counters(reset=True)
+        c = o.gemm(A, W)
+        torch.cuda.synchronize()
+        return c, o.counters()["gemm_smallm"]
+
+    with o.options(gemm_smallm=0):
+        c0, n0 = call()
+    c1, n1 = call()
+    with pytest.raises(ZeroDivisionError):
+        with o.options(gemm_smallm=0):
+            1 / 0
+    c2, n2 = call()
+    assert (n0, n1, n2) == (0, 1, 1)
+    assert rel(c0.float(), ref) < TOL[torch.bfloat16] and rel(c1.float(), ref) < TOL[torch.bfloat16]
+    assert torch.equal(c2, c1)

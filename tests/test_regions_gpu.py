@@ -115,9 +115,8 @@ def test_q_prescale_policy_both_paths_both_settings():
     crit = _crit()
     data = _data(cfg, 2)
     res = {}
-    try:
-        for qpre in (1, 0):
-            ops.set_option("attn_qpre", qpre)
+    for qpre in (1, 0):
+        with ops.options(attn_qpre=qpre):
             o0, g0 = _step(model, crit, data, regions=False)
             ops.counters(reset=True)
             o1, g1 = _step(model, crit, data, regions=True)
@@ -126,8 +125,6 @@ def test_q_prescale_policy_both_paths_both_settings():
             _assert_bitwise(o0, o1, f"attn_qpre = {qpre}: outputs")
             _assert_bitwise(g0, g1, f"attn_qpre = {qpre}: gradients", order_tol=5e-3)
             res[qpre] = (o1, g1)
-    finally:
-        ops.set_option("attn_qpre", 1)
     for k in ("slots_head", "slots", "mask"):
         a, b = res[1][0][k].float(), res[0][0][k].float()
         assert float((a - b).abs().max() / b.abs().max()) < 3e-2, k
@@ -144,14 +141,10 @@ def test_regions_defer_is_bitwise_the_per_kernel_second_stages(name, dtype, B):
     model = _build(cfg, dtype)
     crit = _crit()
     data = _data(cfg, B)
-    old = ops.get_option("regions_defer")
-    try:
-        ops.set_option("regions_defer", 0)
+    with ops.options(regions_defer=0):
         o0, g0 = _step(model, crit, data, regions=True)
-        ops.set_option("regions_defer", 1)
+    with ops.options(regions_defer=1):
         o1, g1 = _step(model, crit, data, regions=True)
-    finally:
-        ops.set_option("regions_defer", old)
     _assert_bitwise(o0, o1, f"{name} {dtype} outputs, regions_defer 0 vs 1")
     _assert_bitwise(g0, g1, f"{name} {dtype} gradients, regions_defer 0 vs 1")
 
