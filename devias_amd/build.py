@@ -16,9 +16,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdevias_amd.so")
-SOURCES = ["api.hip", "gemm.hip", "elementwise.hip", "layernorm.hip", "attention.hip", "slot_attn.hip", "loss.hip", "fame.hip", "regions.hip", "probe.hip", "attn_bwd1w.hip"]
+# the GEMM: one unit per kernel family (two where one would compile for too long: gemm128.h, gemm256p.h) + the host side (gemm.hip); first in SOURCES, longest first, so that the longest compiles start first
+GEMM_SOURCES = ["gemm256.hip", "gemm256p.hip", "gemm128_bf16.hip", "gemm128_f32.hip", "gemm_ss.hip", "gemm256w.hip", "gemm_smallm.hip", "gemm.hip"]
+SOURCES = GEMM_SOURCES + ["attn_bwd1w.hip", "slot_attn.hip", "layernorm.hip", "attention.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-HEADERS = ["common.h", "roctx_shim.h", "attn1w.h"]
+HEADERS = ["common.h", "roctx_shim.h", "attn1w.h", "gemm_common.h", "gemm_tile256.h", "gemm128.h", "gemm256p.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wno-unused-result",
          "-fno-gpu-rdc", "-mllvm", "-amdgpu-early-inline-all=true",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]   # keep MFMA accumulators in VGPRs: no v_accvgpr_* shuffles around the VALU epilogues
@@ -79,7 +81,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             o = os.path.join(CSRC, s.replace(".hip", ".o"))
             if os.path.exists(o):
                 os.remove(o)
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), int(os.environ.get("MAX_JOBS", 16)), os.cpu_count() or 4)) as ex:
         objs = list(ex.map(_compile, SOURCES))
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)

@@ -508,7 +508,7 @@ __global__ __launch_bounds__(NW * 64, 2) void mhsa_fwd32_bf16_kernel(const bf16*
         lsum += ls0 + ls1;
     };
     // O^T += V^T P^T of tile t: 16-key steps kk = 2 kb + s2; transposed reads from inline assembly (before the builtin the compiler waits
-    // vmcnt(0), i.e. for the LDS-DMA in flight -- gemm.hip)
+    // vmcnt(0), i.e. for the LDS-DMA in flight -- gemm_tile256.h)
     auto pv_tile = [&](int t, const bf16x8 (&pf)[2][2]) {
         const char* imgV = stage(t) + 8192;
 #pragma unroll

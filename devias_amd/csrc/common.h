@@ -19,7 +19,7 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 int devias_set_error(int code, const char* fmt, ...);
 void devias_count(int id);                                  // launch counters (api.hip): DEVIAS_CNT_* of include/devias_amd.h
-extern "C" int32_t devias_policy_gemm_cus(void);             // gemm.hip: CUs the big-tile grids count on (device CUs - option gemm_reserve_cus)
+extern "C" int32_t devias_policy_gemm_cus(void);             // gemm.hip (the GEMM's host side): CUs the big-tile grids count on (device CUs - option gemm_reserve_cus)
 
 // ---- process-wide options ----------------------------------------------------------------------------------------------------------------
 // ONE row per option: (id, name for devias_set_option / devias_get_option, environment variable read once at first use, default).  What each value

@@ -1,1955 +1,17 @@
-// Fused GEMM for gfx950: C[M,N] = epi( op(A)[M,K] * op(B)[K,N] ), MFMA 16x16x32 bf16 / 16x16x4 f32, fp32 accumulate.
-//
-// 128x128 output tile per 256-thread workgroup (4 waves as 2x2, 64x64 per wave = 4x4 MFMA tiles).
-// Operands are staged global -> registers -> LDS (next tile's loads are issued before the MFMAs of the
-// current one).  Two LDS images exist per operand kind:
-//   KC ("k contiguous", e.g. activations [M,K], nn.Linear weights [N,K]): [128 rows][BK] with the 16-byte
-//      chunk index XOR (row & 7) -> conflict-free ds_read_b128 fragment reads;
-//   KS ("k strided", e.g. dY for wgrad, W for dgrad): [BK][128 cols], 32-byte windows XOR f(k) -> conflict-free
-//      ds_read_b64_tr_b16 transposing reads (gfx950), which deliver the MFMA fragment with k contiguous per lane.
-// The MFMA is issued as mfma(Bfrag, Afrag) so each lane ends up with 4 CONSECUTIVE output columns of one row
-// (8-byte bf16 / 16-byte f32 epilogue accesses, bias as one float4).
-#include "common.h"
+// devias_gemm for gfx950: C[M,N] = epi( op(A)[M,K] * op(B)[K,N] ).  The host side: validation, the choice of a kernel family and its launch (each family's
+// kernel and template ladder live in units of their own: gemm128.h, gemm256.hip, gemm256p.h, gemm256w.hip, gemm_ss.hip, gemm_smallm.hip; what they
+// share: gemm_common.h, gemm_tile256.h), the dynamic tile queue's ring, the split-K / column-sum reduction kernels and the in-step timer.
+#include "gemm_common.h"
 #include <mutex>
-#include <utility>
 #include <atomic>
+
+using namespace gemm_units;
 
 namespace {
 
-enum { BM = 128, BN = 128, NTHREADS = 256 };
-
-struct GemmP {
-    const void* A; const void* B; void* C;
-    int M, N, K, lda, ldb, ldc;
-    const float* bias; int act;
-    const void* aux_in; void* aux_out; int ld_aux;
-    const void* res; int ldr, res_mod;
-    float beta; int c_f32; int vec_c; int vec16;
-    float* ws; int k_per_split; int split_k;
-    int tiles_m, tiles_n;
-    const float* row_scale; int rows_per_scale;   // optional per-sample scale of (acc+bias, act) before the residual (stochastic depth)
-    float* colsum_part;   // optional: per-(wave row-tile) partial column sums of the stored output, [M / (16*NI)][N]
-    int group_m;          // tile rasterisation: GM row-tiles per group (m fastest inside a group); 1 = n fastest
-    int epi_swap;         // 1 = register-transposed epilogue (epilogue_swap), 0 = LDS-staged (epilogue_staged)
-    int debug;            // timing ablations, compiled in only with -DDEVIAS_GEMM_DEBUG (option "gemm_debug"): 1 = one K-tile, 2 = no epilogue,
-                          // 4 = no LDS-DMA after tile 0, 8 = s_memrealtime stamps into ws, 64 = epilogue without its C stores,
-                          // 128 = without its pre-activation stores, 256 = without the GELU / dGELU polynomial, 1024 = the fc1 epilogue saves GELU'(pre) in place of pre
-                          // (a second polynomial there), 2048 = the dGELU epilogue multiplies by the saved value (with 1024: the "saved derivative" form, measured in DESIGN.md section 5 round 5)
-    int aux_nt;           // persistent kernels: the saved pre-activation (aux_out) is stored with the non-temporal hint (option gemm_aux_nt, bit 0)
-    int c_nt;             // persistent kernels: so is the output C (option gemm_aux_nt, bits 2 / 3: the host decides per launch)
-    int tail_split;       // gemm256p_kernel: split the tiles of the last partial round between two workgroups (128-row halves)
-    int64_t sA, sB, sC;   // batched launches (128x128 kernel, blockIdx.z = batch index): element strides between consecutive problems
-    // dynamic tile queue of gemm256p_kernel<.., true>: this launch's queue slot (8 per-XCD heads, one per 128-byte line, + the line of claim masks; all zero
-    // when the launch starts), the ring slot this launch zeroes for a later one, and the item list of a queue (nwhole whole tiles, then the halves of the split tail tiles)
-    // for the two queue lengths that occur: [0] = queues of ntiles / 8 + 1 tiles, [1] = of ntiles / 8
-    unsigned int* tq; unsigned int* tq_clear; int tq_nwhole[2], tq_items[2];
-};
-
-#ifdef DEVIAS_GEMM_DEBUG
-#define GDBG(flag) (p.debug & (flag))
-#else
-#define GDBG(flag) 0
-#endif
-
-template <typename T> struct Tr;
-template <> struct Tr<bf16> {
-    enum { BK = 64, KSTEP = 32, CH = 8, KC_BYTES = 128 * 128, KS_BYTES = 64 * 256 };
-    typedef bf16x8 frag;
-};
-template <> struct Tr<float> {
-    enum { BK = 16, KSTEP = 4, CH = 4, KC_BYTES = 128 * 20 * 4, KS_BYTES = 16 * 144 * 4 };
-    typedef float frag;
-};
-
-// ---- LDS byte offsets of one element ---------------------------------------------------------------
-__device__ __forceinline__ int ks_f(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
-template <typename T> __device__ __forceinline__ int off_kc(int row, int k);
-template <typename T> __device__ __forceinline__ int off_ks(int k, int col);
-template <> __device__ __forceinline__ int off_kc<bf16>(int row, int k) {
-    return row * 128 + ((((k >> 3) ^ (row & 7))) << 4) + (k & 7) * 2;
-}
-template <> __device__ __forceinline__ int off_ks<bf16>(int k, int col) {
-    return k * 256 + ((((col >> 4) ^ ks_f(k))) << 5) + (col & 15) * 2;
-}
-template <> __device__ __forceinline__ int off_kc<float>(int row, int k) { return (row * 20 + k) * 4; }
-template <> __device__ __forceinline__ int off_ks<float>(int k, int col) { return (k * 144 + col) * 4; }
-
-// ---- staging: global -> registers ------------------------------------------------------------------
-// One operand tile is 128 x BK elements = 256 threads x NCH 16-byte chunks.
-template <typename T, bool KSTRIDED, bool VEC>
-struct Stage {
-    enum { BK = Tr<T>::BK, CH = Tr<T>::CH, NCH = 128 * BK / CH / NTHREADS, NEL = 128 * BK / NTHREADS };
-    u32x4 v[NCH];
-
-    // ptr: operand base; ld: leading dim; r0: first row/col of the 128-wide dim; R: its extent; k0: first k; kend: exclusive k bound
-    __device__ __forceinline__ void load(const T* __restrict__ ptr, int ld, int r0, int R, int k0, int kend, int tid) {
-        if constexpr (VEC) {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                int c = tid + i * NTHREADS;
-                int row, k;
-                if constexpr (!KSTRIDED) { row = c / (BK / CH); k = (c % (BK / CH)) * CH; }
-                else { k = c / (128 / CH); row = (c % (128 / CH)) * CH; }
-                int gr = r0 + row, gk = k0 + k;
-                bool ok = gr < R && gk < kend;
-                const T* src = KSTRIDED ? ptr + (int64_t)gk * ld + gr : ptr + (int64_t)gr * ld + gk;
-                u32x4 z = {0u, 0u, 0u, 0u};
-                v[i] = ok ? *reinterpret_cast<const u32x4*>(src) : z;
-            }
-        } else {
-            // scalar guarded path: pack CH consecutive elements (along the contiguous dim) into one chunk
-            T* e = reinterpret_cast<T*>(v);
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                int c = tid + i * NTHREADS;
-                int row, k;
-                if constexpr (!KSTRIDED) { row = c / (BK / CH); k = (c % (BK / CH)) * CH; }
-                else { k = c / (128 / CH); row = (c % (128 / CH)) * CH; }
-#pragma unroll
-                for (int j = 0; j < CH; ++j) {
-                    int gr = r0 + row + (KSTRIDED ? j : 0), gk = k0 + k + (KSTRIDED ? 0 : j);
-                    bool ok = gr < R && gk < kend;
-                    const T* src = KSTRIDED ? ptr + (int64_t)gk * ld + gr : ptr + (int64_t)gr * ld + gk;
-                    e[i * CH + j] = ok ? *src : from_f32<T>(0.f);
-                }
-            }
-        }
-    }
-
-    __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            int c = tid + i * NTHREADS;
-            int off;
-            if constexpr (!KSTRIDED) { int row = c / (BK / CH), k = (c % (BK / CH)) * CH; off = off_kc<T>(row, k); }
-            else { int k = c / (128 / CH), col = (c % (128 / CH)) * CH; off = off_ks<T>(k, col); }
-            *reinterpret_cast<u32x4*>(lds + off) = v[i];
-        }
-    }
-};
-
-// ---- fragment reads ----------------------------------------------------------------------------------
-// tile16 = index of the 16-wide tile inside the 128-wide dim, ks = k-step inside BK
-template <bool KSTRIDED>
-__device__ __forceinline__ bf16x8 read_frag(const char* lds, int base16, int ks, int lane, bf16*) {
-    if constexpr (!KSTRIDED) {
-        int row = base16 + (lane & 15);
-        int kch = ks * 4 + (lane >> 4);
-        return *reinterpret_cast<const bf16x8*>(lds + row * 128 + ((kch ^ (row & 7)) << 4));
-    } else {
-        int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-        int k = ks * 32 + g * 8 + q;
-        int col = base16 + 4 * p;
-        typedef __attribute__((address_space(3))) bf16x4* lp;
-        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(lds + off_ks<bf16>(k, col)));
-        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(lds + off_ks<bf16>(k + 4, col)));
-        bf16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return r;
-    }
-}
-template <bool KSTRIDED>
-__device__ __forceinline__ float read_frag(const char* lds, int base16, int ks, int lane, float*) {
-    int i = base16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    if constexpr (!KSTRIDED) return *reinterpret_cast<const float*>(lds + off_kc<float>(i, k));
-    else return *reinterpret_cast<const float*>(lds + off_ks<float>(k, i));
-}
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-template <typename F, int... N> __device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, N...>) { (f(std::integral_constant<int, N>{}), ...); }
-template <int COUNT, typename F> __device__ __forceinline__ void static_for(F&& f) { static_for_seq(f, std::make_integer_sequence<int, COUNT>{}); }
-
-// bijective XCD-aware remap: consecutive logical tile ids land on one XCD (private L2) -- speed only
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (bid >> 3);
-}
-
-
-// ---- LDS-staged epilogue (bf16 activations, full tiles, 16-byte aligned rows) ---------------------------------------
-// The MFMA layout gives each lane 4 columns of 16 different rows: stored directly that is 16 partial 128-B lines per
-// wave-instruction and the store path, not HBM, bounds the kernel (measured: 105 of 260 us on the QKV shape).  So the
-// accumulators (+bias) of one wave go through a private fp32 LDS region ([16*TPP rows][64 cols], 256-B rows, 16-B chunk
-// index XOR (row & 15): conflict-free both ways), TPP row-tiles per pass, and every global access of the epilogue --
-// C, the saved pre-activation, the residual, aux_in, split-K slabs -- is row-contiguous, 16 bytes per lane, whole lines.
-template <int NI, int TPP>
-__device__ __forceinline__ void epilogue_staged(const GemmP& p, f32x4 (&acc)[NI][4], char* reg, int mrow0, int ncol0, int z, int lane) {
-    const int lm = lane & 15, g = lane >> 4;
-    const int rr = lane >> 3, c0 = (lane & 7) * 2;     // read-back: row inside an 8-row group, first of two 16-B chunks
-    const int ncol = ncol0 + (lane & 7) * 8;           // first of this lane's 8 output columns
-    f32x4 bias4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        bias4[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + ncol0 + j * 16 + g * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-    const bf16* res = reinterpret_cast<const bf16*>(p.res);
-    const bf16* aux_in = reinterpret_cast<const bf16*>(p.aux_in);
-    bf16* aux_out = reinterpret_cast<bf16*>(p.aux_out);
-    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // column sums of what this lane stores (bias gradient fusion)
-#pragma unroll
-    for (int pass = 0; pass < NI / TPP; ++pass) {
-#pragma unroll
-        for (int i4 = 0; i4 < TPP; ++i4) {
-            const int row = i4 * 16 + lm;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *reinterpret_cast<f32x4*>(reg + row * 256 + (((4 * j + g) ^ (row & 15)) << 4)) = acc[pass * TPP + i4][j] + bias4[j];
-        }
-#pragma unroll
-        for (int it = 0; it < 2 * TPP; ++it) {
-            const int row = it * 8 + rr;
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(reg + row * 256 + ((c0 ^ (row & 15)) << 4));
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(reg + row * 256 + (((c0 + 1) ^ (row & 15)) << 4));
-            float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            const int m = mrow0 + pass * 16 * TPP + row;
-            if (p.split_k > 1) {
-                float* w = p.ws + ((int64_t)z * p.M + m) * p.N + ncol;
-                *reinterpret_cast<f32x4*>(w) = lo;
-                *reinterpret_cast<f32x4*>(w + 4) = hi;
-                continue;
-            }
-            if (p.act == DEVIAS_ACT_GELU) {
-                if (aux_out) {
-                    bf16x8 pre = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-                    *reinterpret_cast<bf16x8*>(aux_out + (int64_t)m * p.ld_aux + ncol) = pre;
-                }
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const f32x2 y = gelu_fast2(f32x2{v[e], v[e + 1]});
-                    v[e] = y[0]; v[e + 1] = y[1];
-                }
-            } else if (p.act == DEVIAS_ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if (p.act == DEVIAS_ACT_SIGMOID) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = 1.0f / (1.0f + expf(-v[e]));
-            } else if (p.act == DEVIAS_ACT_DGELU || p.act == DEVIAS_ACT_DRELU) {
-                const bf16x8 a8 = *reinterpret_cast<const bf16x8*>(aux_in + (int64_t)m * p.ld_aux + ncol);
-                if (p.act == DEVIAS_ACT_DGELU) {
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const f32x2 d = dgelu_fast2(f32x2{(float)a8[e], (float)a8[e + 1]});
-                        v[e] *= d[0]; v[e + 1] *= d[1];
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (float)a8[e] > 0.f ? v[e] : 0.f;
-                }
-            }
-            if (p.row_scale) {
-                const float rs = p.row_scale[m / p.rows_per_scale];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= rs;
-            }
-            if (res) {
-                const int mr = p.res_mod > 0 ? m % p.res_mod : m;
-                const bf16x8 r8 = *reinterpret_cast<const bf16x8*>(res + (int64_t)mr * p.ldr + ncol);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] += (float)r8[e];
-            }
-            if (p.colsum_part) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) cs[e] += v[e];
-            }
-            if (p.c_f32) {
-                float* C = reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + ncol;
-                f32x4 o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-                if (p.beta != 0.f) {
-                    o0 += p.beta * *reinterpret_cast<const f32x4*>(C);
-                    o1 += p.beta * *reinterpret_cast<const f32x4*>(C + 4);
-                }
-                *reinterpret_cast<f32x4*>(C) = o0;
-                *reinterpret_cast<f32x4*>(C + 4) = o1;
-            } else {
-                bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-                if (!GDBG(64) || v[0] == 12345.678f)       // ablation: staging + math without the global stores
-                    *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(p.C) + (int64_t)m * p.ldc + ncol) = o;
-            }
-        }
-    }
-    if (p.colsum_part && p.split_k == 1) {
-        // lanes with equal (lane & 7) own the same 8 columns (rows differ): fold the 8 row-lanes, fixed order
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            cs[e] += __shfl_xor(cs[e], 8, 64);
-            cs[e] += __shfl_xor(cs[e], 16, 64);
-            cs[e] += __shfl_xor(cs[e], 32, 64);
-        }
-        if (lane < 8) {
-            float* dst = p.colsum_part + (int64_t)(mrow0 / (16 * NI)) * p.N + ncol;
-            *reinterpret_cast<f32x4*>(dst) = f32x4{cs[0], cs[1], cs[2], cs[3]};
-            *reinterpret_cast<f32x4*>(dst + 4) = f32x4{cs[4], cs[5], cs[6], cs[7]};
-        }
-    }
-}
-
-
-// ---- register-transposed epilogue (bf16 activations, full tiles, 16-byte aligned rows) ---------------------------------------
-// Same contract as epilogue_staged, without LDS: gfx950's v_permlane16_swap exchanges the accumulator quads of lane groups g and
-// g ^ 1, after which lane (row lm, group g) owns 8 CONSECUTIVE columns of one row -- column tile 2*pr + (g & 1), half g >> 1 -- i.e.
-// a 16-byte bf16 piece; one store instruction then writes 16 rows x 64 contiguous bytes.  Measured (tools/exp/store_bw.hip) that
-// pattern stores at 24.8 GB/s per CU vs 26.0 for whole 128-B lines, and the LDS round trip it removes cost more than the stores
-// (qkv shape: staging + arithmetic 35 us, stores 23 us of a 58 us epilogue).
-// DEFER (persistent kernels): the stores of the output (and of the saved pre-activation) are issued from inline asm, and the rows the
-// epilogue reads are ALL requested up front.  The compiler's wait insertion then never sees a pending store: with visible stores it
-// drains the whole memory pipeline before the next tile's first LDS-DMA / MFMA (measured: the store burst of every tile was exposed);
-// this way the burst drains under the next K-iteration's 64 MFMAs per wave.  (Waits the compiler computes for its own loads are counted
-// in issue order; asm stores issued after such a load only make them stricter, never too weak.)
-__device__ __forceinline__ void store16_asm(const void* sbase, uint32_t voff, u32x4 data) {
-    asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(data), "s"(sbase) : "memory");
-}
-// the same store with the non-temporal hint: for bytes nobody reads before they have left every cache anyway (the saved pre-activation of fc1: read by the backward, ~20 ms later)
-__device__ __forceinline__ void store16_asm_nt(const void* sbase, uint32_t voff, u32x4 data) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" ::"v"(voff), "v"(data), "s"(sbase) : "memory");
-}
-// sum over the 16 lanes of a DPP row, by four DPP adds (quad_perm [1,0,3,2], [2,3,0,1], row_ror:4, row_ror:8) instead of four ds_bpermute shuffles: lane 0 of the row (the
-// only one whose result the epilogues store) adds exactly the pairs the xor-1/2/4/8 butterfly adds, in the same order -- bitwise the same -- without the LDS crossbar round trips
-__device__ __forceinline__ float row16_sum(float t) {
-#define DEVIAS_DPP_ADD(ctrl) t += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(t), ctrl, 0xf, 0xf, false))
-    DEVIAS_DPP_ADD(0xB1); DEVIAS_DPP_ADD(0x4E); DEVIAS_DPP_ADD(0x124); DEVIAS_DPP_ADD(0x128);
-#undef DEVIAS_DPP_ADD
-    return t;
-}
-// SIDE: which rows the epilogue reads, as a compile-time fact (-1 = decided at run time): 0 none, 1 residual, 2 saved pre-activation of
-// dGELU / dReLU.  The persistent kernels need it: a load whose use sits behind a different run-time condition than its issue looks
-// "possibly still pending" to the compiler's wait insertion at the K loop's head, which then drains the memory pipeline every iteration.
-// EPI (round 6): the epilogue's RUN-TIME switches as compile-time facts too -- activation code, bias / saved pre-activation / row scale / column sums present or not.
-// Why: with those decided at run time the compiler keeps every path in the per-piece body and speculates the cheap ones: a plain bias epilogue executed, per
-// 16-row x 64-byte piece, the row-scale multiplies (four v_pk_mul + eight v_cndmask), the column-sum adds of zero, eight register moves that join the
-// activation paths and ~ten scalar branches -- 60 vector instructions where 17 are needed (8 adds, 4 lane-group swaps, 4 converts, the store) -- and the
-// epilogue interval of the persistent kernels is vector-instruction time.  EPI < 0: the generic form (every combination, decided at run time);
-// EPI >= 0: bits 0-2 the activation code, then EPI_BIAS / EPI_AUX / EPI_RS / EPI_CS.  The host picks the instantiation that matches a call's arguments
-// (the encoder block's six epilogues have one each) and falls back to the generic form otherwise; same arithmetic in the same order: bitwise equal (tested).
-enum { EPI_ACT = 7, EPI_BIAS = 8, EPI_AUX = 16, EPI_RS = 32, EPI_CS = 64 };
-template <int NI, bool DEFER = false, int SIDE = -1, int EPI = -1>
-__device__ __forceinline__ void epilogue_swap(const GemmP& p, f32x4 (&acc)[NI][4], int mrow0, int ncol0, int z, int lane) {
-    const int lm = lane & 15, g = lane >> 4;
-    const uint32_t col2 = (uint32_t)(16 * (g & 1) + 8 * (g >> 1)) * 2;
-    const uint32_t vo_c = (uint32_t)lm * (uint32_t)p.ldc * 2 + col2, vo_x = (uint32_t)lm * (uint32_t)p.ld_aux * 2 + col2;
-    constexpr bool BIAS_ON = !(DEFER && SIDE == 2), CS_ON = !(DEFER && SIDE == 1);
-    constexpr bool GEN = EPI < 0;
-    const int act = GEN ? p.act : (EPI & EPI_ACT);
-    const bool on_bias = GEN ? p.bias != nullptr : (EPI & EPI_BIAS) != 0;
-    const bool on_aux = GEN ? p.aux_out != nullptr : (EPI & EPI_AUX) != 0;
-    const bool on_rs = GEN ? p.row_scale != nullptr : (EPI & EPI_RS) != 0;
-    const bool on_cs = GEN ? p.colsum_part != nullptr : (EPI & EPI_CS) != 0;
-    f32x4 bias4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        bias4[j] = (BIAS_ON && on_bias) ? *reinterpret_cast<const f32x4*>(p.bias + ncol0 + j * 16 + g * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-    // DEFER: the stochastic-depth row scales as two SCALARS (rows_per_scale >= 16 * NI, host: the wave's rows span at most two samples);
-    // the register budget of the up-front row fetch also drops what the step never combines (host): bias with SIDE 2, column sums with SIDE 1
-    float rs_lo = 1.f, rs_hi = 1.f;
-    int rs_edge = 0;
-    if constexpr (DEFER) {
-        if (on_rs) {
-            const int r0 = mrow0 / p.rows_per_scale, rl = (p.M - 1) / p.rows_per_scale;
-            rs_lo = p.row_scale[r0]; rs_hi = p.row_scale[r0 < rl ? r0 + 1 : rl];
-            rs_edge = (r0 + 1) * p.rows_per_scale;
-        }
-    }
-    const bf16* res = reinterpret_cast<const bf16*>(p.res);
-    const bf16* aux_in = reinterpret_cast<const bf16*>(p.aux_in);
-    bf16* aux_out = reinterpret_cast<bf16*>(p.aux_out);
-    float cs[2][8];
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) cs[pr][e] = 0.f;
-    // the rows the epilogue reads (residual, or the saved pre-activation of dGELU / dReLU) are fetched PF pieces ahead of their use
-    constexpr int PF = DEFER ? 2 * NI : 4;
-    const bool has_res = SIDE == 1 ? true : (SIDE == -1 ? res != nullptr : false);
-    const bool dact = SIDE == 2 ? true : (SIDE == -1 ? (act == DEVIAS_ACT_DGELU || act == DEVIAS_ACT_DRELU) : false);
-    const bf16* side = has_res ? res : aux_in;
-    const int side_ld = has_res ? p.ldr : p.ld_aux;
-    const bool side_on = SIDE > 0 ? true : (SIDE == 0 ? false : (side != nullptr && p.split_k == 1));
-    bf16x8 sbuf[PF];
-    auto side_load = [&](int n) -> bf16x8 {
-        const int i = n >> 1, pr = n & 1;
-        int m = mrow0 + i * 16 + lm;
-        if (has_res && p.res_mod > 0) m %= p.res_mod;
-        return *reinterpret_cast<const bf16x8*>(side + (int64_t)m * side_ld + ncol0 + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1));      // (the saved pre-activation read non-temporally: -0.02 ms, noise; not kept)
-    };
-    if (side_on) {
-#pragma unroll
-        for (int n = 0; n < PF; ++n) sbuf[n] = side_load(n);
-    }
-    // (the generic form adds a zero bias where there is none; a specialised form without bias skips the add: an accumulator chain that starts at +0 never
-    //  holds -0 unless a negative sum underflows, the only value the add of +0 would change)
-    const bool add_bias = GEN || (BIAS_ON && on_bias);
-    // (Round 6, measured and removed: the specialised forms that read rows doing bias + lane-group exchange of EVERY piece first, in place, while those rows are in flight --
-    //  stamps proj 5.60 -> 5.53, dfc2 10.57 -> 10.52 us per tile, three interleaved bench pairs 45.41 vs 45.40 ms: the first piece's wait is not what the interval is made of.)
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int m = mrow0 + i * 16 + lm;
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-            bf16x8 side8 = sbuf[(i * 2 + pr) % PF];
-            if (side_on && i * 2 + pr + PF < 2 * NI) sbuf[(i * 2 + pr) % PF] = side_load(i * 2 + pr + PF);
-            float v[8];
-            const f32x4 A = add_bias ? acc[i][2 * pr] + bias4[2 * pr] : acc[i][2 * pr], B = add_bias ? acc[i][2 * pr + 1] + bias4[2 * pr + 1] : acc[i][2 * pr + 1];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(A[r]), __float_as_uint(B[r]), false, false);
-                v[r] = __uint_as_float(sw[0]);
-                v[4 + r] = __uint_as_float(sw[1]);
-            }
-            const int ncol = ncol0 + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1);
-            if (!DEFER && p.split_k > 1) {
-                float* w = p.ws + ((int64_t)z * p.M + m) * p.N + ncol;
-                *reinterpret_cast<f32x4*>(w) = f32x4{v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<f32x4*>(w + 4) = f32x4{v[4], v[5], v[6], v[7]};
-                continue;
-            }
-            if (dact) {
-                const bf16x8 a8 = has_res ? *reinterpret_cast<const bf16x8*>(aux_in + (int64_t)m * p.ld_aux + ncol) : side8;
-                if (act == DEVIAS_ACT_DGELU) {
-                    if (GDBG(256) || GDBG(2048)) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] *= (float)a8[e];
-                    } else {
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const f32x2 d = dgelu_fast2(f32x2{(float)a8[e], (float)a8[e + 1]});
-                        v[e] *= d[0]; v[e + 1] *= d[1];
-                    }
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (float)a8[e] > 0.f ? v[e] : 0.f;
-                }
-            } else if (act == DEVIAS_ACT_GELU) {
-                if (on_aux) {
-                    bf16x8 pre = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-                    if (GDBG(1024)) {          // measurement of "save GELU'(pre) instead of pre" (with 2048 in the consumer the pair is a correct dGELU): the second polynomial's cost HERE
-#pragma unroll
-                        for (int e = 0; e < 8; e += 2) {
-                            const f32x2 d = dgelu_fast2(f32x2{v[e], v[e + 1]});
-                            pre[e] = (bf16)d[0]; pre[e + 1] = (bf16)d[1];
-                        }
-                    }
-                    if constexpr (DEFER) {
-                        if (p.aux_nt & 1) store16_asm_nt(aux_out + (int64_t)(mrow0 + i * 16) * p.ld_aux + ncol0 + 32 * pr, vo_x, *reinterpret_cast<const u32x4*>(&pre));
-                        else store16_asm(aux_out + (int64_t)(mrow0 + i * 16) * p.ld_aux + ncol0 + 32 * pr, vo_x, *reinterpret_cast<const u32x4*>(&pre));
-                    }
-                    else if (!GDBG(128) || v[0] == 12345.678f) *reinterpret_cast<bf16x8*>(aux_out + (int64_t)m * p.ld_aux + ncol) = pre;
-                }
-                if (!GDBG(256)) {
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const f32x2 y = gelu_fast2(f32x2{v[e], v[e + 1]});
-                    v[e] = y[0]; v[e + 1] = y[1];
-                }
-                }
-            } else if (act == DEVIAS_ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if (act == DEVIAS_ACT_SIGMOID) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = 1.0f / (1.0f + expf(-v[e]));
-            }
-            if (on_rs) {
-                const float rs = DEFER ? (m >= rs_edge ? rs_hi : rs_lo) : p.row_scale[m / p.rows_per_scale];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= rs;
-            }
-            if (has_res) {
-                const bf16x8 r8 = side8;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] += (float)r8[e];
-            }
-            if (CS_ON && on_cs) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) cs[pr][e] += v[e];
-                // (specialised forms: pin the sums HERE -- with no branch between the pieces the compiler sank all 128 adds behind the last piece and kept every
-                //  piece's values alive for them: 256 registers + scratch, and a scratch reload's vmcnt(0) would expose the tile's whole store burst)
-                if constexpr (!GEN) asm volatile("" : "+v"(cs[pr][0]), "+v"(cs[pr][1]), "+v"(cs[pr][2]), "+v"(cs[pr][3]), "+v"(cs[pr][4]), "+v"(cs[pr][5]), "+v"(cs[pr][6]), "+v"(cs[pr][7]));
-            }
-            if (!DEFER && p.c_f32) {
-                float* C = reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + ncol;
-                f32x4 o0 = {v[0], v[1], v[2], v[3]}, o1 = {v[4], v[5], v[6], v[7]};
-                if (p.beta != 0.f) {
-                    o0 += p.beta * *reinterpret_cast<const f32x4*>(C);
-                    o1 += p.beta * *reinterpret_cast<const f32x4*>(C + 4);
-                }
-                *reinterpret_cast<f32x4*>(C) = o0;
-                *reinterpret_cast<f32x4*>(C + 4) = o1;
-            } else {
-                bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-                if constexpr (DEFER) {
-                    if (p.c_nt) store16_asm_nt(reinterpret_cast<const bf16*>(p.C) + (int64_t)(mrow0 + i * 16) * p.ldc + ncol0 + 32 * pr, vo_c, *reinterpret_cast<const u32x4*>(&o));
-                    else store16_asm(reinterpret_cast<const bf16*>(p.C) + (int64_t)(mrow0 + i * 16) * p.ldc + ncol0 + 32 * pr, vo_c, *reinterpret_cast<const u32x4*>(&o));
-                }
-                else if (!GDBG(64) || v[0] == 12345.678f)
-                    *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(p.C) + (int64_t)m * p.ldc + ncol) = o;
-            }
-            // a specialised form has no branches left between its pieces: without a fence the scheduler interleaves all sixteen and the forms that also carry
-            // column sums run out of registers (256 + scratch); one piece at a time keeps them where the generic form is
-            if constexpr (!GEN) __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if (CS_ON && on_cs && p.split_k == 1) {
-        // the 16 lanes of a group (same g, rows lm = 0..15) own the same columns: fold them in a fixed order
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float t = cs[pr][e];
-                t = row16_sum(t);          // (was four xor shuffles: -0.06 ... -0.09 ms per step, same bits)
-                cs[pr][e] = t;
-            }
-            if (lm == 0) {
-                float* dst = p.colsum_part + (int64_t)(mrow0 / (16 * NI)) * p.N + ncol0 + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1);
-                *reinterpret_cast<f32x4*>(dst) = f32x4{cs[pr][0], cs[pr][1], cs[pr][2], cs[pr][3]};
-                *reinterpret_cast<f32x4*>(dst + 4) = f32x4{cs[pr][4], cs[pr][5], cs[pr][6], cs[pr][7]};
-            }
-        }
-    }
-}
-
-
-// tile id -> (tm, tn): groups of GM row-tiles, m fastest inside a group (GM = 1: n fastest)
-__device__ __forceinline__ void tile_coords(int t, int tiles_m, int tiles_n, int GM, int& tm, int& tn) {
-    if (GM <= 1) { tm = t / tiles_n; tn = t % tiles_n; return; }
-    const int per_group = GM * tiles_n;
-    const int group = t / per_group;
-    const int first_m = group * GM;
-    const int gsz = min(tiles_m - first_m, GM);
-    const int r = t - group * per_group;
-    tm = first_m + r % gsz;
-    tn = r / gsz;
-}
-
-template <typename T, bool TA, bool TB, bool VEC>
-__global__ __launch_bounds__(NTHREADS) void gemm_kernel(GemmP p) {
-    typedef typename Tr<T>::frag frag;
-    constexpr int BK = Tr<T>::BK, KSTEP = Tr<T>::KSTEP;
-    constexpr int A_BYTES = TA ? Tr<T>::KS_BYTES : Tr<T>::KC_BYTES;
-    constexpr int B_BYTES = TB ? Tr<T>::KS_BYTES : Tr<T>::KC_BYTES;
-    __shared__ __attribute__((aligned(16))) char smem[A_BYTES + B_BYTES];
-    char* ldsA = smem;
-    char* ldsB = smem + A_BYTES;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int t = xcd_remap(blockIdx.x, ntiles);
-    const int tm = t / p.tiles_n, tn = t % p.tiles_n;       // n fastest: neighbours share the A row panel
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int z = blockIdx.y;
-    const int kbeg = z * p.k_per_split;
-    const int kend = min(p.K, kbeg + p.k_per_split);
-    const int nk = (kend - kbeg + BK - 1) / BK;
-
-    const T* A = reinterpret_cast<const T*>(p.A) + (int64_t)blockIdx.z * p.sA;
-    const T* B = reinterpret_cast<const T*>(p.B) + (int64_t)blockIdx.z * p.sB;
-    p.C = reinterpret_cast<char*>(p.C) + (int64_t)blockIdx.z * p.sC * (p.c_f32 ? 4 : (int)sizeof(T));
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    Stage<T, TA, VEC> sa;
-    Stage<T, TB, VEC> sb;
-    if (nk > 0) {
-        sa.load(A, p.lda, m0, p.M, kbeg, kend, tid);
-        sb.load(B, p.ldb, n0, p.N, kbeg, kend, tid);
-    }
-    for (int kt = 0; kt < nk; ++kt) {
-        sa.store(ldsA, tid);
-        sb.store(ldsB, tid);
-        __syncthreads();
-        if (kt + 1 < nk) {
-            sa.load(A, p.lda, m0, p.M, kbeg + (kt + 1) * BK, kend, tid);
-            sb.load(B, p.ldb, n0, p.N, kbeg + (kt + 1) * BK, kend, tid);
-        }
-#pragma unroll
-        for (int ks = 0; ks < BK / KSTEP; ++ks) {
-            frag fa[4], fb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[i] = read_frag<TA>(ldsA, wm * 64 + i * 16, ks, lane, (T*)nullptr);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = read_frag<TB>(ldsB, wn * 64 + j * 16, ks, lane, (T*)nullptr);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(fb[j], fa[i], acc[i][j]);
-        }
-        __syncthreads();
-    }
-
-    if constexpr (sizeof(T) == 2) {
-        if (p.vec16 && m0 + BM <= p.M && n0 + BN <= p.N) {       // full tile, 16-byte aligned rows: LDS-staged epilogue
-            epilogue_staged<4, 2>(p, acc, smem + wave * 8192, m0 + wm * 64, n0 + wn * 64, z, lane);
-            return;
-        }
-    }
-    // ---- epilogue: lane holds C[m = .. + (lane&15)][n = .. + 4*(lane>>4) + r], r = 0..3 ----------------
-    const int lm = lane & 15, ln = (lane >> 4) * 4;
-    if (p.split_k > 1) {
-        float* ws = p.ws + (int64_t)z * p.M * p.N;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int m = m0 + wm * 64 + i * 16 + lm;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int n = n0 + wn * 64 + j * 16 + ln;
-                if (p.vec_c && n + 3 < p.N) {
-                    *reinterpret_cast<f32x4*>(ws + (int64_t)m * p.N + n) = acc[i][j];
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (n + r < p.N) ws[(int64_t)m * p.N + n + r] = acc[i][j][r];
-                }
-            }
-        }
-        return;
-    }
-
-    const T* res = reinterpret_cast<const T*>(p.res);
-    const T* aux_in = reinterpret_cast<const T*>(p.aux_in);
-    T* aux_out = reinterpret_cast<T*>(p.aux_out);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int m = m0 + wm * 64 + i * 16 + lm;
-        if (m >= p.M) continue;
-        int mr = p.res_mod > 0 ? m % p.res_mod : m;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int n = n0 + wn * 64 + j * 16 + ln;
-            if (n >= p.N) continue;
-            f32x4 v = acc[i][j];
-            bool full = p.vec_c && (n + 3 < p.N);
-            if (p.bias) {
-                if (full) { f32x4 b = *reinterpret_cast<const f32x4*>(p.bias + n); v += b; }
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (n + r < p.N) v[r] += p.bias[n + r];
-                }
-            }
-            if (p.act == DEVIAS_ACT_GELU) {
-                if (aux_out) {
-                    if (full) store4(aux_out + (int64_t)m * p.ld_aux + n, v);
-                    else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) if (n + r < p.N) aux_out[(int64_t)m * p.ld_aux + n + r] = from_f32<T>(v[r]);
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = gelu_t<T>(v[r]);
-            } else if (p.act == DEVIAS_ACT_RELU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            } else if (p.act == DEVIAS_ACT_SIGMOID) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = 1.0f / (1.0f + expf(-v[r]));
-            } else if (p.act == DEVIAS_ACT_DGELU || p.act == DEVIAS_ACT_DRELU) {
-                f32x4 a;
-                if (full) a = load4(aux_in + (int64_t)m * p.ld_aux + n);
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) a[r] = (n + r < p.N) ? to_f32(aux_in[(int64_t)m * p.ld_aux + n + r]) : 0.f;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    v[r] = (p.act == DEVIAS_ACT_DGELU) ? v[r] * dgelu_t<T>(a[r]) : (a[r] > 0.f ? v[r] : 0.f);
-            }
-            if (p.row_scale) v *= p.row_scale[m / p.rows_per_scale];
-            if (res) {
-                if (full) { f32x4 rr = load4(res + (int64_t)mr * p.ldr + n); v += rr; }
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (n + r < p.N) v[r] += to_f32(res[(int64_t)mr * p.ldr + n + r]);
-                }
-            }
-            if (p.c_f32) {
-                float* C = reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n;
-                if (full) {
-                    if (p.beta != 0.f) { f32x4 o = *reinterpret_cast<f32x4*>(C); v += p.beta * o; }
-                    *reinterpret_cast<f32x4*>(C) = v;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (n + r < p.N) C[r] = v[r] + (p.beta != 0.f ? p.beta * C[r] : 0.f);
-                }
-            } else {
-                T* C = reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n;
-                if (full) store4(C, v);
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (n + r < p.N) C[r] = from_f32<T>(v[r]);
-                }
-            }
-        }
-    }
-}
-
-
-// =====================================================================================================================
-// 256 x 256 x 64 tile, 512 threads (8 waves as 2(M) x 4(N), 128 x 64 per wave), bf16 only, full tiles only.
-// Operands go global -> LDS directly with global_load_lds_dwordx4 (LDS-DMA: no VGPR staging, no ds_write pass) into a
-// 2-stage ring (2 x (32 KiB A + 32 KiB B) = 128 KiB, one workgroup per CU); ONE barrier per K-tile: the loads of tile
-// t+1 are issued right after the barrier that publishes tile t and fly during its 64 MFMAs per wave.
-// LDS-DMA writes 64 lanes x 16 B linearly, so the XOR swizzles of the two images are applied to the per-lane SOURCE
-// address (and again on the fragment reads): same images / same conflict-free reads as the 128 x 128 kernel.
-// =====================================================================================================================
-enum { T2 = 256, NT2 = 512, STAGE2 = 65536 };
-
-__device__ __forceinline__ int off_kc2(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-__device__ __forceinline__ int off_ks2(int k, int col) { return k * 512 + ((((col >> 4) ^ ks_f(k))) << 5) + (col & 15) * 2; }
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef const __attribute__((address_space(1))) void* glb_void_ptr;
-
-// issue the 4 LDS-DMA instructions this wave owns for one 256 x 64 operand tile.  Addressing: everything that varies per instruction
-// (tile origin, K-tile, piece index, wave) is wave-uniform and lives in a scalar base; the per-lane part is ONE 32-bit byte offset per
-// operand layout (two for the k-strided one) -> global_load_lds v_off, s[base] and no 64-bit per-lane pointers held across the K loop.
-__device__ __forceinline__ uint32_t glds_voff_kc(int ld, int lane) {       // 8 rows x 128 B per instruction; chunk XOR (row & 7)
-    return (uint32_t)(((lane >> 3) * ld + (((lane & 7) ^ ((lane >> 3) & 7)) * 8)) * 2);
-}
-__device__ __forceinline__ uint32_t glds_voff_ks(int ld, int lane, int kpar, int i) {   // 2 k-rows x 512 B per instruction; k = 8*wave + 2*i + (lane >> 5)
-    const int klo = (2 * i + (lane >> 5)) & 3;                  // k & 3
-    const int f = klo | (kpar << 2);                            // ks_f(k): (k & 3) | (((k >> 3) & 1) << 2), (k >> 3) & 1 == wave & 1
-    const int slot = lane & 31;
-    return (uint32_t)(((lane >> 5) * ld + ((((slot >> 1) ^ f)) << 4) + (slot & 1) * 8) * 2);
-}
-template <bool KSTRIDED>
-__device__ __forceinline__ void glds_tile(const bf16* __restrict__ ptr, int ld, int r0, int k0, char* lds, int wave, int lane) {
-    if constexpr (!KSTRIDED) {
-        const uint32_t vo = glds_voff_kc(ld, lane);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r8 = wave * 32 + i * 8;                    // 8 rows x 128 B = 1 KiB per instruction
-            const char* ub = reinterpret_cast<const char*>(ptr + (int64_t)(r0 + r8) * ld + k0);
-            __builtin_amdgcn_global_load_lds((glb_void_ptr)(ub + vo), (lds_void_ptr)(lds + r8 * 128), 16, 0, 0);
-        }
-    } else {
-        const uint32_t vo0 = glds_voff_ks(ld, lane, wave & 1, 0), vo1 = glds_voff_ks(ld, lane, wave & 1, 1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k2 = wave * 8 + i * 2;                     // 2 k-rows x 512 B = 1 KiB per instruction
-            const char* ub = reinterpret_cast<const char*>(ptr + (int64_t)(k0 + k2) * ld + r0);
-            __builtin_amdgcn_global_load_lds((glb_void_ptr)(ub + ((i & 1) ? vo1 : vo0)), (lds_void_ptr)(lds + k2 * 512), 16, 0, 0);
-        }
-    }
-}
-
-template <bool KSTRIDED>
-__device__ __forceinline__ bf16x8 read_frag2(const char* lds, int base16, int ks, int lane) {
-    if constexpr (!KSTRIDED) {
-        int row = base16 + (lane & 15);
-        return *reinterpret_cast<const bf16x8*>(lds + off_kc2(row, ks * 4 + (lane >> 4)));
-    } else {
-        int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-        int k = ks * 32 + g * 8 + q;
-        int col = base16 + 4 * p;
-        typedef __attribute__((address_space(3))) bf16x4* lp;
-        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(lds + off_ks2(k, col)));
-        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(lds + off_ks2(k + 4, col)));
-        bf16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return r;
-    }
-}
-
-// Transposing LDS read issued from inline asm.  Why: the compiler cannot see which LDS bytes an in-flight LDS-DMA writes, and for the
-// ds_read_tr builtin (unlike plain C++ LDS loads) it protects itself with s_waitcnt vmcnt(0) before the first such read -- which waits
-// for the NEXT K-tile's DMA and turns a 2-stage ring into a single-stage one.  The asm read is invisible to that logic; the price is
-// that its result is not tracked either: tr_fence() below is the (only) point where the values become usable.
-__device__ __forceinline__ u32x2 ds_read_tr_asm(const char* lds_ptr) {
-    u32x2 r;
-    const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)lds_ptr;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-// One k-strided fragment = two transposing reads.  The halves stay separate register pairs until tr_fence has run: nothing (not even
-// a register copy that assembles the 128-bit operand) may touch them while the reads are in flight.
-struct TrFrag { u32x2 lo, hi; };
-__device__ __forceinline__ TrFrag read_frag2a(const char* lds, int base16, int ks, int lane) {
-    int g = lane >> 4, t = lane & 15, q = t >> 2, pp = t & 3;
-    int k = ks * 32 + g * 8 + q;
-    int col = base16 + 4 * pp;
-    TrFrag f;
-    f.lo = ds_read_tr_asm(lds + off_ks2(k, col));
-    f.hi = ds_read_tr_asm(lds + off_ks2(k + 4, col));
-    return f;
-}
-__device__ __forceinline__ bf16x8 tr_assemble(const TrFrag& f) {
-    const u32x4 r = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
-    return *reinterpret_cast<const bf16x8*>(&r);
-}
-// wait for every outstanding LDS read; the raw halves are operands so that nothing that reads them can be scheduled above the wait
-template <int N>
-__device__ __forceinline__ void tr_fence(TrFrag (&f)[N]) {
-    static_assert(N == 4 || N == 8, "fragment groups of 4 (B) or 8 (A)");
-    if constexpr (N == 4)
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo), "+v"(f[3].hi) :: "memory");
-    else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo), "+v"(f[3].hi),
-                     "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi), "+v"(f[6].lo), "+v"(f[6].hi), "+v"(f[7].lo), "+v"(f[7].hi) :: "memory");
-}
-// plain (compiler-tracked) fragments ride through the same wait so that they, too, are complete after it
-template <int N>
-__device__ __forceinline__ void plain_fence(bf16x8 (&f)[N]) {
-    static_assert(N == 4 || N == 8, "fragment groups of 4 (B) or 8 (A)");
-    if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]) :: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]) :: "memory");
-}
-
-// (Round 6, measured and removed -- profiles/r6_wgrad_kloop.txt: two re-schedules of the k-strided K-tile of the weight-gradient kernel, both bitwise equal, both SLOWER in the
-//  step: progressive counted lgkmcnt waits, row tile i's MFMAs as soon as B and A[0..i] have returned, +0.17 / +0.23 ms; waves 4-7 running half a K-tile behind waves 0-3 so
-//  that the read phase of one wave of a SIMD falls under the MFMA phase of the other, +0.43 / +0.48 ms.  As in round 4, the compiler's schedule stands: what holds this loop at
-//  2.0 us per K-tile is not the order of reads and MFMAs inside a wave or between the two waves of a SIMD.)
-// ---- one K-tile (64 deep) of the 256 x 256 tile: 64 MFMAs per wave ---------------------------------------------------------------------
-// NT layout, order pinned by hand: 16 steps of 4 MFMAs (one A row-tile x 4 B column-tiles); the 8 LDS-DMA instructions of the NEXT K-tile
-// (source origins a_next / b_next = first row of the tile at the K-tile's first k; nullptr = nothing to load) go one per step over the
-// first 8 steps, fragment reads run two steps ahead of their use.  Measured and NOT adopted (profiles/r2e_gemm_kloop_experiments.txt):
-// issuing the 8 LDS-DMA instructions 2 / 4 / 8 per step (+0.4 ... +1.3 % block time), and a rotated schedule with the workgroup barrier
-// after step 12 and the next K-tile's first fragments preloaded under the last 16 MFMAs (fc1 +-0 %, qkv -5 %, 28 more registers).  The K
-// loop runs at 1.55 us per K-tile = 70 % of its MFMA bound at the clock the CUs hold under this load (1.9 GHz, tools/gemm_pstamps.py).
-__device__ __forceinline__ void ktile_nt_pinned(f32x4 (&acc)[8][4], const char* cur, char* nxt, const bf16* a_next, int lda,
-                                                const bf16* b_next, int ldb, int wave, int lane, int wm, int wn) {
-    const char* sA = cur; const char* sB = cur + 32768;
-    const uint32_t vo_a = glds_voff_kc(lda, lane), vo_b = glds_voff_kc(ldb, lane);
-    bf16x8 fb0[4], fb1[4], fa0[4], fa1[4];
-#define G_RA(ks, ih, i) read_frag2<false>(sA, wm * 128 + ((ih) * 4 + (i)) * 16, ks, lane)
-#define G_RB(ks, j) read_frag2<false>(sB, wn * 64 + (j) * 16, ks, lane)
-#define G_MM4(ih, i, fb, fa) _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[(ih) * 4 + (i)][j] = mfma16(fb[j], fa[i], acc[(ih) * 4 + (i)][j]);
-#define G_SB __builtin_amdgcn_sched_barrier(0);
-#define G_DMA(n) { const int r8 = wave * 32 + ((n) & 3) * 8; \
-                   const char* ub = reinterpret_cast<const char*>((n) < 4 ? a_next + (int64_t)r8 * lda : b_next + (int64_t)r8 * ldb); \
-                   __builtin_amdgcn_global_load_lds((glb_void_ptr)(ub + ((n) < 4 ? vo_a : vo_b)), (lds_void_ptr)(nxt + ((n) < 4 ? 0 : 32768) + r8 * 128), 16, 0, 0); }
-    G_SB
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fb0[j] = G_RB(0, j);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa0[i] = G_RA(0, 0, i);
-    G_SB
-    G_MM4(0, 0, fb0, fa0) G_DMA(0) fa1[0] = G_RA(0, 1, 0); fb1[0] = G_RB(1, 0); G_SB
-    G_MM4(0, 1, fb0, fa0) G_DMA(1) fa1[1] = G_RA(0, 1, 1); fb1[1] = G_RB(1, 1); G_SB
-    G_MM4(0, 2, fb0, fa0) G_DMA(2) fa1[2] = G_RA(0, 1, 2); fb1[2] = G_RB(1, 2); G_SB
-    G_MM4(0, 3, fb0, fa0) G_DMA(3) fa1[3] = G_RA(0, 1, 3); fb1[3] = G_RB(1, 3); G_SB
-    G_MM4(1, 0, fb0, fa1) G_DMA(4) fa0[0] = G_RA(1, 0, 0); G_SB
-    G_MM4(1, 1, fb0, fa1) G_DMA(5) fa0[1] = G_RA(1, 0, 1); G_SB
-    G_MM4(1, 2, fb0, fa1) G_DMA(6) fa0[2] = G_RA(1, 0, 2); G_SB
-    G_MM4(1, 3, fb0, fa1) G_DMA(7) fa0[3] = G_RA(1, 0, 3); G_SB
-    G_MM4(0, 0, fb1, fa0) fa1[0] = G_RA(1, 1, 0); G_SB
-    G_MM4(0, 1, fb1, fa0) fa1[1] = G_RA(1, 1, 1); G_SB
-    G_MM4(0, 2, fb1, fa0) fa1[2] = G_RA(1, 1, 2); G_SB
-    G_MM4(0, 3, fb1, fa0) fa1[3] = G_RA(1, 1, 3); G_SB
-    G_MM4(1, 0, fb1, fa1) G_SB
-    G_MM4(1, 1, fb1, fa1) G_SB
-    G_MM4(1, 2, fb1, fa1) G_SB
-    G_MM4(1, 3, fb1, fa1) G_SB
-#undef G_RA
-#undef G_RB
-#undef G_MM4
-#undef G_SB
-#undef G_DMA
-}
-
-// any layout, compiler-scheduled: fragments of one 32-deep k-step, then its 32 MFMAs; k-strided operands use the asm transposing reads
-template <bool TA, bool TB>
-__device__ __forceinline__ void ktile_generic(f32x4 (&acc)[8][4], const char* cur, int lane, int wm, int wn) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 fa[8], fb[4];
-        if constexpr (TA || TB) {
-            // plain (compiler-tracked) reads first, the asm transposing reads after them, then the waits; fragments are assembled
-            // only after their wait
-            TrFrag ta[TA ? 8 : 1], tb[TB ? 4 : 1];
-            if constexpr (!TB) { _Pragma("unroll") for (int j = 0; j < 4; ++j) fb[j] = read_frag2<false>(cur + 32768, wn * 64 + j * 16, ks, lane); }
-            if constexpr (!TA) { _Pragma("unroll") for (int i = 0; i < 8; ++i) fa[i] = read_frag2<false>(cur, wm * 128 + i * 16, ks, lane); }
-            if constexpr (TB) { _Pragma("unroll") for (int j = 0; j < 4; ++j) tb[j] = read_frag2a(cur + 32768, wn * 64 + j * 16, ks, lane); }
-            if constexpr (TA) { _Pragma("unroll") for (int i = 0; i < 8; ++i) ta[i] = read_frag2a(cur, wm * 128 + i * 16, ks, lane); }
-            if constexpr (TB) { tr_fence(tb); _Pragma("unroll") for (int j = 0; j < 4; ++j) fb[j] = tr_assemble(tb[j]); } else plain_fence(fb);
-            if constexpr (TA) { tr_fence(ta); _Pragma("unroll") for (int i = 0; i < 8; ++i) fa[i] = tr_assemble(ta[i]); } else plain_fence(fa);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = read_frag2<TB>(cur + 32768, wn * 64 + j * 16, ks, lane);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) fa[i] = read_frag2<TA>(cur, wm * 128 + i * 16, ks, lane);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(fb[j], fa[i], acc[i][j]);
-    }
-}
-
-template <bool TA, bool TB, int PIN = 0>
-__global__ __launch_bounds__(NT2) void gemm256_kernel(GemmP p) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE2];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    int t, z;
-    if (gridDim.y == 1 && p.split_k > 1) {
-        // Split-K launched as ONE list of (slab z, tile) pairs in XCD-major order: XCD x (block ids congruent to x mod 8) takes the x-th eighth of the list, i.e. ~32
-        // consecutive tiles of ONE slab.  Workgroups of a slab read the same K range (rows of both operands, for the weight gradient) and differ only in the column blocks:
-        // 32 tiles of one slab are ~11 x 3 column blocks, 14 operand blocks for 32 workgroups, held by the XCD's L2 while the workgroups stream through K together.
-        // The (tile, slab) grid put ~4.5 tiles of EVERY slab on each XCD: seven K ranges per L2, 2.7 x the operand bytes from the fabric (profiles/r4_wgrad_xcd.txt).
-        const int total = ntiles * p.split_k, per = (total + 7) >> 3;
-        const int j = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-        if (j >= total || (int)(blockIdx.x >> 3) >= per) return;
-        z = j / ntiles; t = j - z * ntiles;
-    } else {
-        t = xcd_remap(blockIdx.x, ntiles);
-        z = blockIdx.y;
-    }
-    int tm, tn;
-    tile_coords(t, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
-    const int m0 = tm * T2, n0 = tn * T2;
-    const int kbeg = z * p.k_per_split;
-    const int kend = min(p.K, kbeg + p.k_per_split);
-    int nk = (kend - kbeg) / 64;
-    if (GDBG(1)) nk = min(nk, 1);
-    const bf16* A = reinterpret_cast<const bf16*>(p.A);
-    const bf16* B = reinterpret_cast<const bf16*>(p.B);
-
-#ifdef DEVIAS_GEMM_DEBUG
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
-    if (GDBG(8)) st0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (nk > 0) {
-        glds_tile<TA>(A, p.lda, m0, kbeg, smem, wave, lane);
-        glds_tile<TB>(B, p.ldb, n0, kbeg, smem + 32768, wave, lane);
-    }
-    for (int kt = 0; kt < nk; ++kt) {
-#ifdef DEVIAS_GEMM_DEBUG
-        if (GDBG(8) && kt == 0) st1 = __builtin_amdgcn_s_memrealtime();
-#endif
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA for tile kt has landed
-        __syncthreads();
-#ifdef DEVIAS_GEMM_DEBUG
-        if (GDBG(8) && kt == 0) st2 = __builtin_amdgcn_s_memrealtime();
-#endif
-        char* cur = smem + (kt & 1) * STAGE2;
-        char* nxt = smem + ((kt + 1) & 1) * STAGE2;
-        if constexpr (!TA && !TB && PIN != 0) {
-            const int kn = kbeg + (kt + 1 < nk ? kt + 1 : kt) * 64;       // last tile: harmless re-read into the free stage
-            ktile_nt_pinned(acc, cur, nxt, A + (int64_t)m0 * p.lda + kn, p.lda, B + (int64_t)n0 * p.ldb + kn, p.ldb, wave, lane, wm, wn);
-        } else {
-            if (kt + 1 < nk && !GDBG(4)) {
-                glds_tile<TA>(A, p.lda, m0, kbeg + (kt + 1) * 64, nxt, wave, lane);
-                glds_tile<TB>(B, p.ldb, n0, kbeg + (kt + 1) * 64, nxt + 32768, wave, lane);
-            }
-            ktile_generic<TA, TB>(acc, cur, lane, wm, wn);
-        }
-    }
-
-    // ---- epilogue ------------------------------------------------------------------------------------------------
-    // The MFMA layout gives each lane 4 columns of 16 different rows: stored directly that is 16 partial 128-B lines per
-    // wave-instruction and the store path, not HBM, bounds the kernel (measured: 105 of 260 us on the QKV shape).  Default: the
-    // register-transposed epilogue (epilogue_swap); option gemm_epi = 0: through LDS (the operand ring is dead by now: one 16 KiB
-    // fp32 region per wave, two passes of 64 rows), every global access row-contiguous, 16 bytes per lane.
-#ifdef DEVIAS_GEMM_DEBUG
-    if (GDBG(8)) {
-        st3 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0) {
-            unsigned long long* d = reinterpret_cast<unsigned long long*>(p.ws) + (size_t)blockIdx.x * 6;
-            d[0] = st0; d[1] = st1; d[2] = st2; d[3] = st3;
-            d[4] = __builtin_amdgcn_s_getreg(0x1800 | 20) /* HW_REG_XCC_ID */; d[5] = t;
-        }
-    }
-    if (GDBG(2) && acc[0][0][0] != 12345.678f) return;
-#endif
-    if constexpr (PIN == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing re-read must land before the LDS is released
-    if (p.epi_swap) { epilogue_swap<8>(p, acc, m0 + wm * 128, n0 + wn * 64, z, lane); return; }
-    __syncthreads();                                   // every wave is done reading the operand stages
-    epilogue_staged<8, 4>(p, acc, smem + wave * 16384, m0 + wm * 128, n0 + wn * 64, z, lane);
-}
-
-
-// ---- pieces of a split tail tile (gemm256p_kernel) --------------------------------------------------------------------------------------------------------------
-// piece code: -1 = the whole tile; 0 / 1 = the two 128-row halves (round 3); 16 + i = third i (row tiles [0, 5) [5, 11) [11, 16) of the tile's sixteen 16-row tiles: at most
-// five per wave row, the middle third three in each); 32 + i = quarter i (four row tiles each).  A wave row (wm) owns row tiles [8 wm, 8 wm + 8): its share [il, ih).
-__device__ __forceinline__ void piece_rows(int code, int& lo, int& hi) {
-    if (code < 0) { lo = 0; hi = 16; }
-    else if (code < 16) { lo = 8 * code; hi = lo + 8; }
-    else if (code < 32) { const int i = code - 16; lo = i == 0 ? 0 : (i == 1 ? 5 : 11); hi = i == 0 ? 5 : (i == 1 ? 11 : 16); }
-    else { lo = 4 * (code - 32); hi = lo + 4; }
-}
-__device__ __forceinline__ void piece_wave_rows(int code, int wm, int& il, int& ih) {
-    int lo, hi;
-    piece_rows(code, lo, hi);
-    il = max(lo - 8 * wm, 0); ih = min(hi - 8 * wm, 8);
-    if (ih < il) ih = il;
-}
-// does a piece multiply any of the 32 A rows wave w stages (row tiles 2 w, 2 w + 1)?
-__device__ __forceinline__ bool piece_needs_wave_rows(int code, int w) {
-    int lo, hi;
-    piece_rows(code, lo, hi);
-    return 2 * w < hi && 2 * w + 2 > lo;
-}
-// one K-tile of a wave that multiplies only row tiles [IL, IH) of its eight into accumulators of their own (B k-contiguous; compiler-scheduled: a tail piece's K loop is
-// bound by the operand stream -- the whole B tile and a part of A for a part of the MFMAs).  A compile-time range: MFMAs under a run-time condition, anywhere in the
-// kernel, make the register allocator copy accumulators (256 registers + scratch in every instantiation when this was one routine with a run-time range).
-template <int IL, int IH>
-__device__ __forceinline__ void ktile_nt_rows(f32x4 (&acc)[IH - IL][4], const char* cur, int lane, int wm, int wn) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 fb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = read_frag2<false>(cur + 32768, wn * 64 + j * 16, ks, lane);
-#pragma unroll
-        for (int i = IL; i < IH; ++i) {
-            const bf16x8 fa = read_frag2<false>(cur, wm * 128 + i * 16, ks, lane);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i - IL][j] = mfma16(fb[j], fa, acc[i - IL][j]);
-        }
-    }
-}
-
-// =====================================================================================================================
-// Persistent form of the 256 x 256 kernel (split_k == 1, A k-contiguous): one workgroup per CU walks a static list of tiles and the
-// K-tile stream of the 2-stage LDS-DMA ring runs ACROSS tile boundaries -- the first K-tile of the next tile is requested before the
-// last K-tile of the current one is multiplied, so its fetch (an HBM / L2 round trip that nothing hides in the one-tile-per-workgroup
-// kernel) lands under those MFMAs and the register-only epilogue (epilogue_swap).  The epilogue's stores are left in flight:
-// the wait at the top of the next tile's first K-tile is a COUNTED vmcnt that covers the LDS-DMA only (vmcnt is in issue order and
-// every wave issues >= 16 stores after the DMA), so the output drains under the next tile's MFMAs.
-// Tile order: XCD x (block ids congruent to x mod 8) owns the same contiguous range of logical tiles as in xcd_remap; its G/8 workgroups
-// stride through it together, so at any moment an XCD works on ~32 consecutive tiles (operand panels shared in its L2).
-// =====================================================================================================================
-// ---- dynamic tile queue (DYN): queue words, the published-item word, the dequeue ---------------------------------------------------------
-// Ring of queue slots in the code object (zero at load): launch n uses slot n % TQ_RING and zeroes slot (n + TQ_RING / 2) % TQ_RING for the launch
-// that will use it TQ_RING / 2 launches later (stream order makes the zeroes land long before; no reset pass, no host memset).
-// One slot = 16 lines of 128 bytes (a word that 256 workgroups hit at once is worth a line of its own: one word takes ~88 atomics per microsecond):
-// line y < 8 holds the HEAD of XCD queue y (tickets for the items behind the reserved ones), line 8 + y its CLAIM MASK (bit i = reserved item i is taken).
-enum { TQ_RING = 64, TQ_LINE = 32 /* uint32 per line */, TQ_SLOT = 16 * TQ_LINE, TQ_MASKS = 8 * TQ_LINE * 4 /* byte offset of the first mask */, TQ_NONE = 0x0fffffff };
+// the tile-queue ring (layout: gemm_common.h).  No kernel names it: the host finds it with hipGetSymbolAddress (tile_queue_slot below) and hands a launch its slot
+// in GemmP, so it is defined HERE and nowhere else -- a definition in a shared header would give every unit's code object a ring of its own.
 __device__ unsigned int g_tile_queue[TQ_RING][TQ_SLOT];
-
-// Returning agent-scope atomics by lane 0 (or lanes 0-15) of the calling wave, issued from inline asm under a hand-set EXEC mask: invisible to the compiler's
-// wait insertion (a visible pending load would turn the K loop's counted waits into vmcnt(0) drains); the result is usable after the caller's next
-// s_waitcnt vmcnt(0) that names it.  Wave 0 only, all 64 lanes active at the call.  Each block starts with s_nop 4: the slot pointer may have just been
-// reloaded from a lane of the SGPR-spill VGPR (v_readlane = a VALU write of an SGPR), and a vector-memory instruction that reads an SGPR written by the
-// VALU needs 5 wait states which the compiler's hazard recogniser does not insert inside inline asm (found as a memory fault at an address with a stale
-// high half in the -DDEVIAS_GEMM_DEBUG build, where the pointer lives in a spill lane).
-// The dequeue: ticket = head[queue]++, by lane 0.  (Measured and not kept: the same instruction on 16 lanes, the other 15 adding 0 to the other heads and the
-// claim masks, so that the ticket arrives with a snapshot of every queue and an empty-handed workgroup knows without a waited look that nothing is left: the
-// look it saves costs 1.7 us once per workgroup and launch, the 16-fold atomic traffic cost the step +0.4 ms.)
-__device__ __forceinline__ void tq_issue(unsigned& ticket, unsigned int* slot, int queue) {
-    const unsigned voff = (unsigned)queue * (TQ_LINE * 4), one = 1u;
-    asm volatile("s_nop 4\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add %0, %1, %2, %3 sc0\n\ts_mov_b64 exec, -1" : "+v"(ticket) : "v"(voff), "v"(one), "s"(slot) : "memory");
-}
-__device__ __forceinline__ void tq_issue_claim(unsigned& old, unsigned int* slot, int queue, unsigned bit) {   // old = mask[queue]; mask[queue] |= bit
-    const unsigned voff = TQ_MASKS + (unsigned)queue * (TQ_LINE * 4);
-    asm volatile("s_nop 4\n\ts_mov_b64 exec, 1\n\tglobal_atomic_or %0, %1, %2, %3 sc0\n\ts_mov_b64 exec, -1" : "+v"(old) : "v"(voff), "v"(bit), "s"(slot) : "memory");
-}
-__device__ __forceinline__ void tq_issue_peek(unsigned& snap, unsigned int* slot, int lane) {             // lanes 0-7: the heads, 8-15: the masks (add 0)
-    const unsigned voff = (unsigned)(lane & 15) * (TQ_LINE * 4), zero = 0u;
-    asm volatile("s_nop 4\n\ts_mov_b64 exec, 0xffff\n\tglobal_atomic_add %0, %1, %2, %3 sc0\n\ts_mov_b64 exec, -1" : "+v"(snap) : "v"(voff), "v"(zero), "s"(slot) : "memory");
-}
-// WAIT = false: the readers poll for the tag, nobody needs the write to have completed at any particular point
-template <bool WAIT>
-__device__ __forceinline__ void tq_publish(char* word, unsigned seq, int code) {
-    const unsigned v = ((seq & 15u) << 28) | ((unsigned)code & 0x0fffffffu);
-    const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) char*)word;
-    if constexpr (WAIT) asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" ::"v"(addr), "v"(v) : "memory");
-    else asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-// the item published for position `seq` of this workgroup's item stream: >= 0 (queue << 20 | index), TQ_NONE, or -2 = not published (yet)
-__device__ __forceinline__ int tq_read(const char* word, unsigned seq) {
-    unsigned v;
-    const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)word;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    v = __builtin_amdgcn_readfirstlane(v);
-    return (v >> 28) == (seq & 15u) ? (int)(v & 0x0fffffffu) : -2;
-}
-
-template <bool TB, int SIDE, bool DYN, int EPI = -1>
-__global__ __launch_bounds__(NT2) void gemm256p_kernel(GemmP p) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE2 + (DYN ? 16 : 0)];     // (+ the published next item: ONE LDS object -- a second __shared__ object makes the compiler fence every LDS read behind the LDS-DMA in flight)
-    const int tid = threadIdx.x, lane = tid & 63;
-#ifdef DEVIAS_GEMM_DEBUG
-    const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
-#endif
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int nk = p.K / 64;
-    const bf16* A = reinterpret_cast<const bf16*>(p.A);
-    const bf16* B = reinterpret_cast<const bf16*>(p.B);
-    // this XCD-group's logical tile range and this workgroup's stride through it (gridDim.x is a multiple of 8)
-    const int xcd = blockIdx.x & 7, stride = gridDim.x >> 3;
-    const int q = ntiles >> 3, r = ntiles & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int cnt = q + (xcd < r ? 1 : 0);
-    const int li0 = blockIdx.x >> 3;
-    int li = li0;
-    if constexpr (!DYN) { if (li >= cnt) return; }
-    auto coords = [&](int l, int& m0, int& n0) {
-        int tm, tn;
-        tile_coords(base + l, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
-        m0 = tm * T2; n0 = tn * T2;
-    };
-    // Tail split: the last, partial round of the group (rem tiles for `stride` workgroups) leaves stride - rem CUs idle for a whole tile time.  When
-    // 2 rem <= stride every tail tile goes to TWO workgroups, each computing one 128-row half: in the other half's waves (wm != half) only the operand
-    // staging and the barriers run.  The two wave rows of a workgroup share the SIMDs pairwise, so the active row has the matrix cores to itself and the
-    // tile's K loop takes a bit more than half its time; every output element is computed by the same wave code as before (bitwise equal).
-    const int rfull = cnt / stride, rem = cnt - rfull * stride;
-    const bool split = p.tail_split != 0 && rfull >= 1 && rem > 0 && 2 * rem <= stride;
-    // Round 6: thirds and quarters.  A half tile costs 0.7 of a tile, not 0.5 (its K loop streams the whole B tile and half of A for half the MFMAs, its epilogue is the
-    // active waves' full one: profiles/r6_gemm_pstamps.txt); with 3 rem <= stride (the 588-tile shapes: 9-10 tail tiles for 32 workgroups) the tail tiles go to THREE
-    // workgroups, with 4 rem <= stride (fc1: 6 tail tiles) to FOUR: less K-loop stream per piece and a third / a quarter of the epilogue.  Static lists, B k-contiguous,
-    // no column sums (option gemm_tail_split >= 3 / 4; 2 = halves only).
-    const int parts = (!split || DYN || TB || p.colsum_part != nullptr || p.tail_split < 3) ? 2 : min(min(p.tail_split, 4), stride / rem);
-    // STATIC list (DYN = false): this workgroup's k-th tile: (logical index, piece code: -1 = whole tile, see piece_rows); false = none
-    auto tile_at = [&](int k, int& l, int& half) -> bool {
-        half = -1;
-        if (k < rfull) { l = li0 + k * stride; return true; }
-        if (k > rfull) return false;
-        if (split) {
-            if (li0 >= parts * rem) return false;
-            l = rfull * stride + li0 / parts;
-            half = (parts == 2 ? 0 : (parts == 3 ? 16 : 32)) + li0 % parts;
-            return true;
-        }
-        if (li0 >= rem) return false;
-        l = rfull * stride + li0;
-        return true;
-    };
-    // DYNAMIC queue (DYN = true).  Item i of XCD queue y: the whole tile base_y + i for i < nwhole_y, then the two 128-row halves of each tail tile (the same
-    // items the static list hands out; only WHO computes an item is decided at run time).  Which workgroup computes a tile does not change a bit of it.
-    //   * The first `stride` items of a queue are RESERVED, one per workgroup of that XCD: a workgroup starts on its own (no round trip before the first
-    //     LDS-DMA) and claims it with an atomic OR on the queue's mask word, whose answer arrives with that first K-tile.
-    //   * The items behind them are handed out by tickets of the queue's head word.  A workgroup always holds its current item and the next one (whose
-    //     first K-tile the stream prefetches); the dequeue for the one after is issued by wave 0 during the last K-tile of a tile, is OLDER than that
-    //     iteration's LDS-DMA (so the counted wait of the tile switch covers it) and is read a whole tile later, again under the last K-tile: wave 0
-    //     publishes the item through the LDS word behind the ring and every wave picks it up after its epilogue.  The K loop is the static kernel's.
-    //   * A workgroup whose queue is empty looks at all eight heads and masks at once (one 16-lane instruction), pulls from another XCD's queue, and when
-    //     every head is used up takes reserved items nobody has claimed -- those of workgroups that have not found a CU yet because another kernel holds
-    //     it (RCCL's during backward; bench.py --cu-hog).  Such a workgroup later finds its claim refused and every queue empty, and leaves: a held or
-    //     slowed CU costs its share of the work, not a straggler's tile list.  Only these end-of-launch searches are waited for.
-    char* const tq_word = smem + 2 * STAGE2;
-    // the queue geometry and the slot pointer as OPAQUE scalars: otherwise every use re-loads them from the kernel-argument segment (an s_load round
-    // trip on wave 0's critical path once per tile); opaque values stay in SGPRs or in a lane of the spill VGPR (one v_readlane)
-    int nwhole_a = p.tq_nwhole[0], nwhole_b = p.tq_nwhole[1], items_a = p.tq_items[0], items_b = p.tq_items[1];
-    unsigned int* tq = p.tq;
-    if constexpr (DYN) asm volatile("" : "+s"(nwhole_a), "+s"(nwhole_b), "+s"(items_a), "+s"(items_b), "+s"(tq));
-    auto qgeom = [&](int y, int& qbase, int& nwhole, int& items) {
-        qbase = y < r ? y * (q + 1) : r * (q + 1) + (y - r) * q;
-        nwhole = y < r ? nwhole_a : nwhole_b;
-        items = y < r ? items_a : items_b;
-    };
-    auto decode = [&](int code, int& m0, int& n0, int& half) {
-        const int y = code >> 20, i = code & 0xfffff;
-        int qbase, nwhole, items;
-        qgeom(y, qbase, nwhole, items);
-        const int l = i < nwhole ? i : nwhole + ((i - nwhole) >> 1);
-        half = i < nwhole ? -1 : ((i - nwhole) & 1);
-        int tm, tn;
-        tile_coords(qbase + l, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
-        m0 = tm * T2; n0 = tn * T2;
-    };
-    int fq = xcd;                                          // wave 0: the queue whose head the outstanding dequeue went to
-    bool fdead = false;                                    // wave 0: nothing is left anywhere
-    unsigned ticket = 0, seq = 0;                          // seq = items published to this workgroup so far
-    // wave 0, after a wait that covers the dequeue from queue fq: the item (>= 0), or -2 = that queue's head is used up
-    auto settle = [&]() -> int {
-        const int t = stride + (int)__builtin_amdgcn_readfirstlane(ticket);
-        int qbase, nwhole, items;
-        qgeom(fq, qbase, nwhole, items);
-        return t < items ? ((fq << 20) | t) : -2;
-    };
-    // wave 0, waited round trips (end of a launch only): look at every head and mask, pull from the first queue that still has tickets (own XCD's
-    // neighbours first), else claim an unclaimed reserved item; TQ_NONE when there is nothing
-    auto find_elsewhere = [&]() -> int {
-        const int lane_f = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const unsigned wmask = stride >= 32 ? 0xffffffffu : ((1u << stride) - 1u);
-        for (int attempt = 0; attempt < 256 && !fdead; ++attempt) {
-            unsigned snap = 0;
-            tq_issue_peek(snap, tq, lane_f);
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(snap) :: "memory");
-            int pick = -1, kind = 0;
-            unsigned bit = 0;
-            for (int d = 1; d <= 8 && pick < 0; ++d) {
-                const int y = (xcd + d) & 7;
-                int qbase, nwhole, items;
-                qgeom(y, qbase, nwhole, items);
-                if (stride + (int)__builtin_amdgcn_readlane(snap, y) < items) pick = y;
-            }
-            for (int d = 0; d < 8 && pick < 0 && !(p.debug & 512); ++d) {     // (gemm_debug & 512: reserved items are not taken over -- bisecting aid)
-                const int y = (xcd + d) & 7;
-                const unsigned avail = ~(unsigned)__builtin_amdgcn_readlane(snap, 8 + y) & wmask;
-                if (avail) { pick = y; kind = 1; bit = avail & (0u - avail); }
-            }
-            if (pick < 0) { fdead = true; break; }
-            if (kind == 0) {
-                fq = pick;
-                tq_issue(ticket, tq, fq);
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(ticket) :: "memory");
-                const int c = settle();
-                if (c != -2) return c;
-            } else {
-                unsigned old = 0;
-                tq_issue_claim(old, tq, pick, bit);
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(old) :: "memory");
-                if (!((unsigned)__builtin_amdgcn_readfirstlane(old) & bit)) return (pick << 20) | (int)__builtin_ctz(bit);
-            }
-        }
-        fdead = true;
-        return (int)TQ_NONE;
-    };
-    if constexpr (DYN) {
-        if (blockIdx.x == 0 && tid < 16)                   // (from asm: the compiler's wait insertion never sees a store pending)
-            asm volatile("s_nop 4\n\tglobal_store_dword %0, %1, %2 sc1" ::"v"((unsigned)tid * (TQ_LINE * 4)), "v"(0u), "s"(p.tq_clear) : "memory");
-    }
-    int tk = 0, half = -1, halfn = -1;
-    int m0 = 0, n0 = 0, m0n = 0, n0n = 0;
-    bool has_next = false;
-    int ncode = -2;
-#ifdef DEVIAS_GEMM_DEBUG
-    // gemm_debug & 8: thread 0 logs (100 MHz clock << 4 | code) into ws + 64 * blockIdx.x: 1 = first K-tile of a tile about to be multiplied,
-    // 2 = K loop done, 3 = epilogue done (stores issued), 4 = first K-iteration of the next tile done (its wait passed)
-    int nlog = 0;
-    // (with fused column sums the partials own the head of ws: the stamps then live behind them, at float offset M / 128 * N)
-    unsigned long long* const stamp_base = reinterpret_cast<unsigned long long*>(p.ws + (p.colsum_part ? (size_t)(p.M / 128) * p.N : 0));
-    auto stamp = [&](int code) {
-        if (GDBG(8) && tid == 0 && nlog < 64) {
-            // codes >= 8 log the SHADER clock counter instead (s_memtime): with the matching 100 MHz stamps that gives the clock the CU really runs at
-            const unsigned long long v = ((code >= 8 ? __builtin_amdgcn_s_memtime() : __builtin_amdgcn_s_memrealtime()) << 4) | (unsigned long long)code;
-            asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"((uint32_t)nlog * 8), "v"(v), "s"(stamp_base + (size_t)blockIdx.x * 64) : "memory");
-        }
-        ++nlog;
-    };
-#define PSTAMP(c) stamp(c)
-    if (GDBG(8) && tid == 0) {           // slot 63: the workgroup's entry time
-        const unsigned long long v = (t_entry << 4) | 7ull;
-        asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"((uint32_t)63 * 8), "v"(v), "s"(stamp_base + (size_t)blockIdx.x * 64) : "memory");
-    }
-#else
-#define PSTAMP(c)
-#endif
-    f32x4 acc[8][4];
-    {
-        unsigned claim = 0;
-        if constexpr (!DYN) {
-            (void)tile_at(0, li, half);
-            coords(li, m0, n0);
-        } else {
-            // start on the reserved item; the claim and the dequeue of the second item travel with the first K-tile's LDS-DMA
-            if (wave == 0) {
-                tq_issue_claim(claim, tq, xcd, 1u << li0);
-                tq_issue(ticket, tq, fq);
-            }
-            decode((xcd << 20) | li0, m0, n0, half);
-        }
-        glds_tile<false>(A, p.lda, m0, 0, smem, wave, lane);
-        glds_tile<TB>(B, p.ldb, n0, 0, smem + 32768, wave, lane);
-        if constexpr (!DYN) {
-            int ln = li;
-            has_next = tile_at(1, ln, halfn);
-            m0n = m0; n0n = n0;
-            if (has_next) coords(ln, m0n, n0n);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (!DYN) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(claim), "+v"(ticket) :: "memory");
-            if (wave == 0) {
-                int c0 = ((unsigned)__builtin_amdgcn_readfirstlane(claim) >> li0) & 1u ? -2 : ((xcd << 20) | li0);    // refused: somebody took it while this
-                int c1 = settle();                                                                              // workgroup was waiting for a CU
-                if (c0 == -2) { c0 = c1 != -2 ? c1 : find_elsewhere(); c1 = -2; }
-                if (c0 == (int)TQ_NONE) c1 = c0;
-                else if (c1 == -2) c1 = find_elsewhere();
-                tq_publish<true>(tq_word, 0, c0);
-                tq_publish<true>(tq_word + 4, 1, c1);
-                if (c1 != (int)TQ_NONE && !fdead) tq_issue(ticket, tq, fq);
-            }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const int code = tq_read(tq_word, 0);
-            if (code == (int)TQ_NONE) return;              // every queue was empty: this workgroup came too late to be needed (its DMA has landed)
-            if (code != ((xcd << 20) | li0)) {             // (rare) the reserved item was gone: restage the first K-tile of the item found instead
-                decode(code, m0, n0, half);
-                __builtin_amdgcn_s_barrier();
-                glds_tile<false>(A, p.lda, m0, 0, smem, wave, lane);
-                glds_tile<TB>(B, p.ldb, n0, 0, smem + 32768, wave, lane);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            ncode = tq_read(tq_word + 4, 1);
-            has_next = ncode != (int)TQ_NONE;
-            m0n = m0; n0n = n0;
-            if (has_next) decode(ncode, m0n, n0n, halfn);
-            seq = 2;
-        }
-        bool act = half < 0 || wm == half;                    // (wave-uniform; thirds / quarters never run in this loop: see `tail_piece` below)
-        bool tail_piece = false;
-        int gtail = 0;
-        // ONE flat loop over the K-tile stream (ring stage = g & 1); the wait for K-tile g + 1 sits at the END of iteration g so that the loop has
-        // no first-iteration special case (a peeled copy is where the compiler re-inserts full vmcnt drains)
-        for (int g = 0, kt = 0;; ++g) {
-            __builtin_amdgcn_s_barrier();                      // K-tile g has landed for every wave, and everyone is done reading stage (g + 1) & 1
-            asm volatile("" ::: "memory");
-            if (kt == 0) { PSTAMP(1); PSTAMP(9); }
-            char* cur = smem + (g & 1) * STAGE2;
-            char* nxt = smem + ((g + 1) & 1) * STAGE2;
-            // source of K-tile g + 1: this tile's next one, or the next tile's first; at the very end a harmless re-read
-            const bool same = kt + 1 < nk;
-            const int am = (same || !has_next) ? m0 : m0n, bn = (same || !has_next) ? n0 : n0n;
-            const int kn = same ? (kt + 1) * 64 : (has_next ? 0 : kt * 64);
-            // the lane id is recomputed per K-tile (v_mbcnt) and made opaque: the per-lane LDS / LDS-DMA offsets derived from it are then cheap VALU work of
-            // every iteration instead of registers that stay live across the epilogue, whose register peak is the kernel's (-14 registers)
-            int lane_k = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            asm volatile("" : "+v"(lane_k));
-            // does K-tile g + 1 need the A rows this wave stages?  Not if it belongs to a half tile of the OTHER wave row (nobody multiplies them; tail_split >= 2).
-            // With the static lists a half tile is a workgroup's last item; with the queues it can have a successor, whose first K-tile is staged by ITS halves
-            // (a wave that multiplies the current tile stages its rows in any case)
-            // (K-tile g + 1 belongs to the current item, or to the next one's first K-tile; a wave that multiplies all of its row tiles stages its rows in any case)
-            const bool stage_a = p.tail_split < 2 || act || (DYN && !same && has_next && (halfn < 0 || wm == halfn));
-            if constexpr (!TB) {
-                if (act) ktile_nt_pinned(acc, cur, nxt, A + (int64_t)am * p.lda + kn, p.lda, B + (int64_t)bn * p.ldb + kn, p.ldb, wave, lane_k, wm, wn);
-                else {                                       // the other half's waves of a split tail tile: staging only -- and of B only: the A rows a wave
-                                                               // stages (32 wave + ...) are the rows of ITS half, which nobody multiplies (tail_split >= 2)
-                    if (stage_a) glds_tile<false>(A, p.lda, am, kn, nxt, wave, lane_k);
-                    glds_tile<false>(B, p.ldb, bn, kn, nxt + 32768, wave, lane_k);
-                }
-            } else {
-                if (stage_a) glds_tile<false>(A, p.lda, am, kn, nxt, wave, lane_k);
-                glds_tile<true>(B, p.ldb, bn, kn, nxt + 32768, wave, lane_k);
-                if (act) ktile_generic<false, true>(acc, cur, lane_k, wm, wn);
-            }
-            if (same) {
-                ++kt;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's LDS-DMA for K-tile g + 1 has landed (and, DYN, wave 0's dequeue has returned)
-                if (kt == 1) PSTAMP(4);
-                continue;
-            }
-            PSTAMP(2); PSTAMP(10);
-            int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            asm volatile("" : "+v"(lane_e));                   // opaque: keeps the epilogue's per-lane address arithmetic out of the registers that live across the K loop
-            if (act) epilogue_swap<8, true, SIDE, EPI>(p, acc, m0 + wm * 128, n0 + wn * 64, 0, lane_e);
-            if (!has_next) break;
-            int m0x = 0, n0x = 0, halfx = -1;
-            bool issued = false;                               // (wave 0) one dequeue was issued BEHIND the epilogue's stores
-            if constexpr (DYN) {
-                PSTAMP(5);
-                // The item after `next`, found while the epilogue's stores drain (every wave is about to sit in the counted wait below for that long anyway):
-                // its dequeue was issued at the previous tile switch and every K-iteration's vmcnt(0) since has covered it (>= 2 K-tiles per tile, checked by
-                // the host).  Wave 0 reads the ticket, publishes the item and issues the following dequeue; every wave then reads the word -- no barrier
-                // orders that, so until the tag matches -- and decodes it
-                if (wave == 0) {
-                    asm volatile("" : "+v"(ticket));           // (the ticket is read here, not where the compiler last saw it written)
-                    int c = fdead ? (int)TQ_NONE : settle();
-                    if (c == -2) c = find_elsewhere();
-                    tq_publish<false>(tq_word, seq, c);
-                    issued = c != (int)TQ_NONE && !fdead;
-                    if (issued) tq_issue(ticket, tq, fq);
-                }
-                do { ncode = tq_read(tq_word, seq); } while (ncode == -2);
-                ++seq;
-                if (ncode != (int)TQ_NONE) decode(ncode, m0x, n0x, halfx);
-                PSTAMP(6);
-            }
-            // the epilogue issued >= 16 stores per wave AFTER the DMA of the next tile's first K-tile: wait for the DMA only, the stores drain under the next MFMAs.
-            // (Static list: a tile with a successor is a whole tile, every wave has run the epilogue.  Dynamic queue: a half tile can be followed by an item
-            // pulled from another XCD's queue; the waves that only staged it have no stores behind their DMA and wait for everything.)
-            // (wave 0's dequeue is one more operation behind the DMA: counted too, or the wait would be for the first store)
-            if (DYN && !act) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if !defined(TQ_EXP) || TQ_EXP != 1
-            else if (DYN && issued) asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
-#endif
-            else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            PSTAMP(3);
-            kt = 0;
-            ++tk;
-            m0 = m0n; n0 = n0n; half = halfn;
-            if (!DYN && !TB && half >= 16) { tail_piece = true; gtail = g + 1; break; }      // a third / a quarter of a tail tile: its own loop below (its first K-tile has landed)
-            act = half < 0 || wm == half;
-            if constexpr (!DYN) {
-                int ln = li;
-                has_next = tile_at(tk + 1, ln, halfn);
-                if (has_next) coords(ln, m0n, n0n);
-            } else {
-                has_next = ncode != (int)TQ_NONE;
-                if (has_next) { m0n = m0x; n0n = n0x; halfn = halfx; }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        // ---- a third / a quarter of a tail tile (static lists, B k-contiguous, no column sums: `parts` above) -------------------------------------------------------------
-        // The workgroup's last item, run by its own K loop on accumulators of its own, the wave's row tiles a compile-time range: the K-tile stream continues (the piece's
-        // first K-tile was requested under the previous tile's last K-tile and has landed), every wave stages B and the A rows some wave multiplies, a wave with row tiles
-        // multiplies them and runs the epilogue over just those; waves of one workgroup take different branches here with the same barriers in each.
-        if constexpr (!DYN && !TB && !(EPI >= 0 && (EPI & EPI_CS))) {
-            if (tail_piece) {
-                int il, ih;
-                piece_wave_rows(half, wm, il, ih);
-                auto run = [&](auto ilc, auto ihc) {
-                    constexpr int IL = decltype(ilc)::value, IH = decltype(ihc)::value, NR = IH > IL ? IH - IL : 1;
-                    f32x4 tacc[NR][4];
-#pragma unroll
-                    for (int i = 0; i < NR; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) tacc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const bool stage_a = p.tail_split < 2 || piece_needs_wave_rows(half, wave);
-                    for (int kt = 0, g = gtail; kt < nk; ++kt, ++g) {
-                        __builtin_amdgcn_s_barrier();          // K-tile g has landed for every wave, and everyone is done reading stage (g + 1) & 1
-                        asm volatile("" ::: "memory");
-                        char* cur = smem + (g & 1) * STAGE2;
-                        char* nxt = smem + ((g + 1) & 1) * STAGE2;
-                        int lane_k = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                        asm volatile("" : "+v"(lane_k));
-                        if (kt + 1 < nk) {
-                            if (stage_a) glds_tile<false>(A, p.lda, m0, (kt + 1) * 64, nxt, wave, lane_k);
-                            glds_tile<false>(B, p.ldb, n0, (kt + 1) * 64, nxt + 32768, wave, lane_k);
-                        }
-                        if constexpr (IH > IL) ktile_nt_rows<IL, IH>(tacc, cur, lane_k, wm, wn);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's LDS-DMA for K-tile g + 1 has landed
-                    }
-                    if constexpr (IH > IL) {
-                        int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                        asm volatile("" : "+v"(lane_e));
-                        epilogue_swap<NR, true, SIDE, EPI>(p, tacc, m0 + wm * 128 + IL * 16, n0 + wn * 64, 0, lane_e);
-                    }
-                };
-                using std::integral_constant;
-                if (il >= ih) run(integral_constant<int, 0>{}, integral_constant<int, 0>{});
-                else if (il == 0 && ih == 5) run(integral_constant<int, 0>{}, integral_constant<int, 5>{});
-                else if (il == 5 && ih == 8) run(integral_constant<int, 5>{}, integral_constant<int, 8>{});
-                else if (il == 0 && ih == 3) run(integral_constant<int, 0>{}, integral_constant<int, 3>{});
-                else if (il == 3 && ih == 8) run(integral_constant<int, 3>{}, integral_constant<int, 8>{});
-                else if (il == 0 && ih == 4) run(integral_constant<int, 0>{}, integral_constant<int, 4>{});
-                else run(integral_constant<int, 4>{}, integral_constant<int, 8>{});
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the trailing re-read must land before the LDS is released
-    }
-}
-
-
-// =====================================================================================================================
-// Four-wave form of the persistent 256 x 256 kernel (gemm256w_kernel): ONE wave per SIMD, 128 x 128 per wave, the 256 accumulator
-// registers of a wave in AGPRs (the register file is 512 per lane at this occupancy; the MFMA takes its C / D operand from either half).
-// Why (tools/gemm_mscan.py, profiles/r3h_*): per round of tiles the eight-wave kernel needs 26-27 us at K = 768 where the vendor library's
-// kernel of this shape (four waves of 128 x 128) needs 22-23.  Per K-tile a 128 x 128 wave tile reads 128 KiB of fragments from LDS instead
-// of 192 KiB, and with the whole tile's fragments of BOTH k-steps in registers half-way through the K-tile the stage it occupies is
-// free early: the LDS-DMA of K-tile g + 2 goes into the stage of K-tile g while g is still being multiplied (two K-tiles in flight on a
-// two-stage ring).  Per K-tile and wave: 128 MFMAs in 32 groups of 4 (one A row-tile x 4 B column-tiles), pinned order:
-//   groups  0.. 7   k-step 0, rows 0-3; the 16 fragment reads of k-step 1 ride along (2 per group)
-//   groups  8.. 9   k-step 0, row 4;  then lgkmcnt(0) + barrier #1: every wave holds all of K-tile g -> its stage may be overwritten
-//   groups 10..25   rest of k-step 0, k-step 1; the 16 LDS-DMA instructions of K-tile g + 2 ride along (1 per group)
-//   group  26       vmcnt(16) (everything older than those 16 has landed: K-tile g + 1) + barrier #2: K-tile g + 1 is visible
-//   groups 26..31   the 16 fragment reads of K-tile g + 1, k-step 0, ride along; lgkmcnt(0) at the end
-// The K-tile stream runs across tile boundaries as in gemm256p_kernel; results are bitwise those of the other 256 x 256 kernels (same
-// MFMA chain per output element: K-tiles in order, k-steps in order).
-// =====================================================================================================================
-enum { NTW = 256 };
-
-// the 256 accumulator registers of gemm256w_kernel, by literal name (see W_MM4)
-#define DEVIAS_A10(b) "a" #b "0", "a" #b "1", "a" #b "2", "a" #b "3", "a" #b "4", "a" #b "5", "a" #b "6", "a" #b "7", "a" #b "8", "a" #b "9"
-template <int I> __device__ __forceinline__ void acc_zero1() { asm volatile("v_accvgpr_write_b32 a[%c0], 0" ::"i"(I)); }
-template <int... I> __device__ __forceinline__ void acc_zero_seq(std::integer_sequence<int, I...>) { (acc_zero1<I>(), ...); }
-// every AGPR is claimed here once (the clobber list is what makes the kernel descriptor allocate them)
-__device__ __forceinline__ void acc_claim() {
-    asm volatile("" ::: DEVIAS_A10(), DEVIAS_A10(1), DEVIAS_A10(2), DEVIAS_A10(3), DEVIAS_A10(4), DEVIAS_A10(5), DEVIAS_A10(6), DEVIAS_A10(7), DEVIAS_A10(8), DEVIAS_A10(9),
-                 DEVIAS_A10(10), DEVIAS_A10(11), DEVIAS_A10(12), DEVIAS_A10(13), DEVIAS_A10(14), DEVIAS_A10(15), DEVIAS_A10(16), DEVIAS_A10(17), DEVIAS_A10(18), DEVIAS_A10(19),
-                 DEVIAS_A10(20), DEVIAS_A10(21), DEVIAS_A10(22), DEVIAS_A10(23), DEVIAS_A10(24), "a250", "a251", "a252", "a253", "a254", "a255");
-}
-__device__ __forceinline__ void acc_zero() { acc_zero_seq(std::make_integer_sequence<int, 256>{}); }
-template <int I> __device__ __forceinline__ float acc_read1() { float x; asm volatile("v_accvgpr_read_b32 %0, a[%c1]" : "=v"(x) : "i"(I)); return x; }
-
-// Epilogue of gemm256w_kernel: the wave's 128 x 128 tile in ONE pass of 32 pieces (column half h, row tile i, tile pair pr; 16 rows x 64 B per
-// store instruction), same arithmetic in the same order as epilogue_swap (acc + bias -> lane-group exchange -> GELU -> row scale -> + residual ->
-// bf16), so the results are bitwise those of the other kernels.  One wave per SIMD: nothing hides a wait, and vmcnt counts in issue order, so
-// every load is REQUESTED before the first store of the tile is issued (bias: 32 registers up front; the rows it reads: a ring of 16 pieces
-// refilled one piece per store, i.e. a wait never sits behind fewer than 16 stores) -- a load issued behind a burst of stores waits for the
-// burst to drain (measured: four quarter-tile passes, each starting with its bias load, cost 17 us per tile instead of 5).
-// the rows the epilogue reads (residual / saved pre-activation), piece n = 16 h + 2 i + pr of the wave's 128 x 128 tile
-template <int SIDE>
-__device__ __forceinline__ bf16x8 side_load_w(const GemmP& p, int mrow0, int ncol0, int lane, int n) {
-    const int lm = lane & 15, g = lane >> 4;
-    const bf16* side = reinterpret_cast<const bf16*>(SIDE == 1 ? p.res : p.aux_in);
-    const int side_ld = SIDE == 1 ? p.ldr : p.ld_aux;
-    const int h = n >> 4, i = (n >> 1) & 7, pr = n & 1;
-    int m = mrow0 + i * 16 + lm;
-    if (SIDE == 1 && p.res_mod > 0) m %= p.res_mod;
-    return *reinterpret_cast<const bf16x8*>(side + (int64_t)m * side_ld + ncol0 + 64 * h + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1));
-}
-
-// sbuf: the first 16 pieces of those rows, requested by the kernel two K-tiles before the tile is done
-template <int SIDE>
-__device__ __forceinline__ void epilogue_w(const GemmP& p, int mrow0, int ncol0, int lane, bf16x8 (&sbuf)[SIDE != 0 ? 16 : 1]) {
-    const int lm = lane & 15, g = lane >> 4;
-    const uint32_t col2 = (uint32_t)(16 * (g & 1) + 8 * (g >> 1)) * 2;
-    const uint32_t vo_c = (uint32_t)lm * (uint32_t)p.ldc * 2 + col2, vo_x = (uint32_t)lm * (uint32_t)p.ld_aux * 2 + col2;
-    constexpr bool BIAS_ON = SIDE != 2, CS_ON = SIDE != 1;       // what the step never combines (host): bias with dGELU / dReLU, column sums with a residual
-    f32x4 bias4[BIAS_ON ? 8 : 1];
-    if constexpr (BIAS_ON) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bias4[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + ncol0 + j * 16 + g * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    float rs_lo = 1.f, rs_hi = 1.f;
-    int rs_edge = 0;
-    if (p.row_scale) {
-        const int r0 = mrow0 / p.rows_per_scale, rl = (p.M - 1) / p.rows_per_scale;
-        rs_lo = p.row_scale[r0]; rs_hi = p.row_scale[r0 < rl ? r0 + 1 : rl];
-        rs_edge = (r0 + 1) * p.rows_per_scale;
-    }
-    bf16* aux_out = reinterpret_cast<bf16*>(p.aux_out);
-    constexpr int PF = 16;
-    auto side_load = [&](int n) -> bf16x8 { return side_load_w<SIDE>(p, mrow0, ncol0, lane, n); };
-    float cs[CS_ON ? 4 : 1][8];                   // column sums of the stored values: [2 h + pr][8 columns of the lane]
-    if constexpr (CS_ON) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) cs[c][e] = 0.f;
-    }
-    static_for<32>([&](auto nc) {
-        constexpr int n = decltype(nc)::value, h = n >> 4, i = (n >> 1) & 7, pr = n & 1;
-        constexpr int ra = 16 * (8 * h + i) + 8 * pr;       // tiles (h, i, 2 pr) and (h, i, 2 pr + 1): eight consecutive accumulator registers
-        const int m = mrow0 + i * 16 + lm;
-        bf16x8 side8 = sbuf[SIDE != 0 ? n % PF : 0];
-        if constexpr (SIDE != 0 && n + PF < 32) sbuf[n % PF] = side_load(n + PF);
-        f32x4 A = f32x4{acc_read1<ra>(), acc_read1<ra + 1>(), acc_read1<ra + 2>(), acc_read1<ra + 3>()};
-        f32x4 B = f32x4{acc_read1<ra + 4>(), acc_read1<ra + 5>(), acc_read1<ra + 6>(), acc_read1<ra + 7>()};
-        if constexpr (BIAS_ON) { A += bias4[4 * h + 2 * pr]; B += bias4[4 * h + 2 * pr + 1]; }
-        else { A += f32x4{0.f, 0.f, 0.f, 0.f}; B += f32x4{0.f, 0.f, 0.f, 0.f}; }      // the other kernels add a zero bias here: -0 -> +0, kept for bitwise equality
-        float v[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(A[r]), __float_as_uint(B[r]), false, false);
-            v[r] = __uint_as_float(sw[0]);
-            v[4 + r] = __uint_as_float(sw[1]);
-        }
-        if constexpr (SIDE == 2) {
-            if (p.act == DEVIAS_ACT_DGELU) {
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const f32x2 d = dgelu_fast2(f32x2{(float)side8[e], (float)side8[e + 1]});
-                    v[e] *= d[0]; v[e + 1] *= d[1];
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (float)side8[e] > 0.f ? v[e] : 0.f;
-            }
-        } else if (p.act == DEVIAS_ACT_GELU) {
-            if (aux_out) {
-                bf16x8 pre = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-                store16_asm(aux_out + (int64_t)(mrow0 + i * 16) * p.ld_aux + ncol0 + 64 * h + 32 * pr, vo_x, *reinterpret_cast<const u32x4*>(&pre));
-            }
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) {
-                const f32x2 y = gelu_fast2(f32x2{v[e], v[e + 1]});
-                v[e] = y[0]; v[e + 1] = y[1];
-            }
-        }
-        if (p.row_scale) {
-            const float rs = m >= rs_edge ? rs_hi : rs_lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] *= rs;
-        }
-        if constexpr (SIDE == 1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += (float)side8[e];
-        }
-        if constexpr (CS_ON) {
-            if (p.colsum_part) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) cs[2 * h + pr][e] += v[e];
-            }
-        }
-        bf16x8 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
-        store16_asm(reinterpret_cast<const bf16*>(p.C) + (int64_t)(mrow0 + i * 16) * p.ldc + ncol0 + 64 * h + 32 * pr, vo_c, *reinterpret_cast<const u32x4*>(&o));
-    });
-    if constexpr (CS_ON) {
-        if (p.colsum_part) {
-            // the 16 lanes of a group (same g, rows lm = 0..15) own the same columns: fold them in a fixed order (as epilogue_swap does)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float t = cs[c][e];
-                    t = row16_sum(t);
-                    cs[c][e] = t;
-                }
-                if (lm == 0) {
-                    float* dst = p.colsum_part + (int64_t)(mrow0 / 128) * p.N + ncol0 + 64 * (c >> 1) + 16 * (2 * (c & 1) + (g & 1)) + 8 * (g >> 1);
-                    *reinterpret_cast<f32x4*>(dst) = f32x4{cs[c][0], cs[c][1], cs[c][2], cs[c][3]};
-                    *reinterpret_cast<f32x4*>(dst + 4) = f32x4{cs[c][4], cs[c][5], cs[c][6], cs[c][7]};
-                }
-            }
-        }
-    }
-}
-
-template <bool TB>
-__device__ __forceinline__ void glds_w(const bf16* __restrict__ a_src, int lda, const bf16* __restrict__ b_src, int ldb, char* stage, int wave, int lane) {
-    const uint32_t vo_a = glds_voff_kc(lda, lane);
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        const int r8 = wave * 64 + n * 8;
-        const char* ub = reinterpret_cast<const char*>(a_src + (int64_t)r8 * lda);
-        __builtin_amdgcn_global_load_lds((glb_void_ptr)(ub + vo_a), (lds_void_ptr)(stage + r8 * 128), 16, 0, 0);
-    }
-    if constexpr (!TB) {
-        const uint32_t vo_b = glds_voff_kc(ldb, lane);
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            const int r8 = wave * 64 + n * 8;
-            const char* ub = reinterpret_cast<const char*>(b_src + (int64_t)r8 * ldb);
-            __builtin_amdgcn_global_load_lds((glb_void_ptr)(ub + vo_b), (lds_void_ptr)(stage + 32768 + r8 * 128), 16, 0, 0);
-        }
-    } else {
-        // k-strided B ([K, N] row-major): wave w owns k rows [16 w, 16 w + 16), 2 k-rows x 512 B per instruction; (k >> 3) & 1 == n >> 2 & 1
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            const int k2 = wave * 16 + n * 2;
-            const uint32_t vo = glds_voff_ks(ldb, lane, (n >> 2) & 1, n & 1);
-            const char* ub = reinterpret_cast<const char*>(b_src + (int64_t)k2 * ldb);
-            __builtin_amdgcn_global_load_lds((glb_void_ptr)(ub + vo), (lds_void_ptr)(stage + 32768 + k2 * 512), 16, 0, 0);
-        }
-    }
-}
-
-// wait until at most N LDS operations of this wave are outstanding (they complete in issue order); the raw halves of the transposing reads are
-// operands so that nothing that reads them can be scheduled above the wait
-template <int N>
-__device__ __forceinline__ void tr_fence_cnt(TrFrag (&f)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(%c16)" : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo), "+v"(f[3].hi),
-                 "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi), "+v"(f[6].lo), "+v"(f[6].hi), "+v"(f[7].lo), "+v"(f[7].hi) : "i"(N) : "memory");
-}
-
-// per-wave constants of the LDS-DMA: one buffer descriptor per operand and K-tile (base = the K-tile's first element), one loop-invariant per-lane
-// offset per instruction form, one SCALAR offset per instruction -> an LDS-DMA instruction costs s_mov m0 + buffer_load ... lds and nothing else
-template <bool TB>
-struct WDma {
-    uint32_t vo_a, vo_b[TB ? 4 : 1];
-    int so_a[8], so_b[8];
-    __amdgpu_buffer_rsrc_t rs_a, rs_b;
-    __device__ __forceinline__ void set_src(const bf16* a_src, const bf16* b_src) {
-        rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(a_src), 0, 0x7fffffff, 0x00020000);
-        rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(b_src), 0, 0x7fffffff, 0x00020000);
-    }
-    __device__ __forceinline__ void init(int lda, int ldb, int wave, int lane) {
-        vo_a = glds_voff_kc(lda, lane);
-        if constexpr (!TB) vo_b[0] = glds_voff_kc(ldb, lane);
-        else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) vo_b[c] = glds_voff_ks(ldb, lane, c >> 1, c & 1);
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            so_a[n] = (wave * 64 + n * 8) * lda * 2;
-            so_b[n] = TB ? (wave * 16 + n * 2) * ldb * 2 : (wave * 64 + n * 8) * ldb * 2;
-        }
-    }
-};
-
-// one K-tile; fa0 / fb0: fragments of k-step 0 of THIS K-tile on entry, of the NEXT one on exit.  TB: B is k-strided in memory ([K, N] row-major, the
-// dgrad layout): its LDS image is the k-strided one of the eight-wave kernels and a fragment is two transposing reads issued from inline asm (see
-// ds_read_tr_asm), complete only behind a fence.  ONE wave per SIMD: whatever is not an MFMA has to issue in the shadow of one (16 cycles), so every
-// MFMA is its own statement and at most one other operation sits between two of them.
-// `next_src(a, b)`: advances the kernel's load cursor and yields the source of the K-tile the NEXT call loads; it runs under the last MFMAs of this
-// one (the scalar address arithmetic of a K-tile costs ~25 instructions: at the loop head nothing would hide them).
-template <bool TB, typename NEXT>
-__device__ __forceinline__ void ktile_w(bf16x8 (&fa0)[8], bf16x8 (&fb0)[8], char* cur, const char* nxt, WDma<TB>& d, NEXT&& next_src,
-                                        int wave, int lane, int wm, int wn) {
-#if defined(__HIP_DEVICE_COMPILE__)      // (the host pass does not know the buffer-load-to-LDS builtin)
-    const __amdgpu_buffer_rsrc_t rs_a = d.rs_a, rs_b = d.rs_b;
-    bf16x8 fa1[8], fb1[8];
-    TrFrag tb[TB ? 8 : 1];
-#define W_RA(F, buf, ks, i) F[i] = read_frag2<false>(buf, wm * 128 + (i) * 16, ks, lane);
-#define W_RB(F, T, buf, ks, j) { if constexpr (!TB) F[j] = read_frag2<false>((buf) + 32768, wn * 128 + (j) * 16, ks, lane); \
-                                 else T[j] = read_frag2a((buf) + 32768, wn * 128 + (j) * 16, ks, lane); }
-    // an MFMA on LITERAL accumulator registers: tile (h, i, jj) lives in a[16 (8 h + i) + 4 jj ...+3].  256 live accumulators fill the AGPR half
-    // exactly; as C++ values (builtin or "+a" operands) the register allocator shuffles them through scratch at every loop head.  Named literally they
-    // are invisible to it: the kernel must (and does: audited in the ISA, tests/test_build_cpu.py) use no AGPR of its own and spill nothing.  Hazards:
-    // the A / B operands are written by LDS reads only (waits: the compiler's for plain reads, tr_fence_cnt for the asm ones; no VALU writes them: audited);
-    // a D is next touched 64 MFMAs later, or by acc_read1() behind the kernel's s_nop pad
-#define W_M(i, h, jj, FB, FA) asm volatile("v_mfma_f32_16x16x32_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" :: "v"(FB[(h) * 4 + (jj)]), "v"(FA[i]), \
-                                           "i"(16 * (8 * (h) + (i)) + 4 * (jj)), "i"(16 * (8 * (h) + (i)) + 4 * (jj) + 3));
-#define W_SB __builtin_amdgcn_sched_barrier(0);
-#define W_DMA(n) { if constexpr ((n) < 8) \
-                       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_void_ptr)(cur + (wave * 64 + (n) * 8) * 128), 16, d.vo_a, d.so_a[n], 0, 0); \
-                   else if constexpr (!TB) \
-                       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_void_ptr)(cur + 32768 + (wave * 64 + ((n) & 7) * 8) * 128), 16, d.vo_b[0], d.so_b[(n) & 7], 0, 0); \
-                   else \
-                       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_void_ptr)(cur + 32768 + (wave * 16 + ((n) & 7) * 2) * 512), 16, \
-                                                                d.vo_b[((((n) & 7) >> 2) & 1) * 2 + ((n) & 1)], d.so_b[(n) & 7], 0, 0); }
-    // group forms: 4 MFMAs of (row tile i, column half h) with nothing / one A read + one B read / one LDS-DMA instruction in between
-#define W_G(i, h, FB, FA) W_M(i, h, 0, FB, FA) W_M(i, h, 1, FB, FA) W_M(i, h, 2, FB, FA) W_M(i, h, 3, FB, FA) W_SB
-#define W_GR(i, h, FB, FA, RA_, RB_) W_M(i, h, 0, FB, FA) W_SB RA_ W_SB W_M(i, h, 1, FB, FA) W_M(i, h, 2, FB, FA) W_SB RB_ W_SB W_M(i, h, 3, FB, FA) W_SB
-#define W_GD(i, h, FB, FA, n) W_M(i, h, 0, FB, FA) W_SB W_DMA(n) W_SB W_M(i, h, 1, FB, FA) W_M(i, h, 2, FB, FA) W_M(i, h, 3, FB, FA) W_SB
-    W_SB
-    W_GR(0, 0, fb0, fa0, W_RA(fa1, cur, 1, 0), W_RB(fb1, tb, cur, 1, 0))
-    W_GR(0, 1, fb0, fa0, W_RA(fa1, cur, 1, 1), W_RB(fb1, tb, cur, 1, 1))
-    W_GR(1, 0, fb0, fa0, W_RA(fa1, cur, 1, 2), W_RB(fb1, tb, cur, 1, 2))
-    W_GR(1, 1, fb0, fa0, W_RA(fa1, cur, 1, 3), W_RB(fb1, tb, cur, 1, 3))
-    W_GR(2, 0, fb0, fa0, W_RA(fa1, cur, 1, 4), W_RB(fb1, tb, cur, 1, 4))
-    W_GR(2, 1, fb0, fa0, W_RA(fa1, cur, 1, 5), W_RB(fb1, tb, cur, 1, 5))
-    W_GR(3, 0, fb0, fa0, W_RA(fa1, cur, 1, 6), W_RB(fb1, tb, cur, 1, 6))
-    W_GR(3, 1, fb0, fa0, W_RA(fa1, cur, 1, 7), W_RB(fb1, tb, cur, 1, 7))
-    W_G(4, 0, fb0, fa0)
-    W_G(4, 1, fb0, fa0)
-    if constexpr (TB) { tr_fence_cnt<0>(tb); _Pragma("unroll") for (int j = 0; j < 8; ++j) fb1[j] = tr_assemble(tb[j]); }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave holds all of the K-tile in registers ...
-    __builtin_amdgcn_s_barrier();                           // #1: ... and so does every other one: the stage may be overwritten
-    W_SB
-    W_GD(5, 0, fb0, fa0, 0)
-    W_GD(5, 1, fb0, fa0, 1)
-    W_GD(6, 0, fb0, fa0, 2)
-    W_GD(6, 1, fb0, fa0, 3)
-    W_GD(7, 0, fb0, fa0, 4)
-    W_GD(7, 1, fb0, fa0, 5)
-    W_GD(0, 0, fb1, fa1, 6)
-    W_GD(0, 1, fb1, fa1, 7)
-    W_GD(1, 0, fb1, fa1, 8)
-    W_GD(1, 1, fb1, fa1, 9)
-    W_GD(2, 0, fb1, fa1, 10)
-    W_GD(2, 1, fb1, fa1, 11)
-    W_GD(3, 0, fb1, fa1, 12)
-    W_GD(3, 1, fb1, fa1, 13)
-    W_GD(4, 0, fb1, fa1, 14)
-    W_GD(4, 1, fb1, fa1, 15)
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");       // everything older than this K-tile's 16 LDS-DMA instructions has landed: the next K-tile
-    __builtin_amdgcn_s_barrier();                           // #2: ... of every wave
-    W_SB
-    // the next K-tile's k-step 0 (TB: the asm reads of B first; the counted fence then leaves the 7 A reads issued behind them in flight); the last
-    // group carries no read, so that the loop head finds the fragments complete, and the cursor arithmetic for the next call instead
-    W_GR(5, 0, fb1, fa1, W_RB(fb0, tb, nxt, 0, 0) W_RB(fb0, tb, nxt, 0, 1), W_RB(fb0, tb, nxt, 0, 2) W_RB(fb0, tb, nxt, 0, 3))
-    W_GR(5, 1, fb1, fa1, W_RA(fa0, nxt, 0, 0), W_RB(fb0, tb, nxt, 0, 4) W_RB(fb0, tb, nxt, 0, 5))
-    W_GR(6, 0, fb1, fa1, W_RB(fb0, tb, nxt, 0, 6) W_RB(fb0, tb, nxt, 0, 7), W_RA(fa0, nxt, 0, 1) W_RA(fa0, nxt, 0, 2))
-    W_GR(6, 1, fb1, fa1, W_RA(fa0, nxt, 0, 3) W_RA(fa0, nxt, 0, 4), W_RA(fa0, nxt, 0, 5))
-    W_GR(7, 0, fb1, fa1, W_RA(fa0, nxt, 0, 6), W_RA(fa0, nxt, 0, 7))
-    const bf16 *a_next, *b_next;
-    W_GR(7, 1, fb1, fa1, next_src(a_next, b_next);, d.set_src(a_next, b_next);)
-    if constexpr (TB) { tr_fence_cnt<7>(tb); _Pragma("unroll") for (int j = 0; j < 8; ++j) fb0[j] = tr_assemble(tb[j]); }
-#undef W_RA
-#undef W_RB
-#undef W_M
-#undef W_SB
-#undef W_DMA
-#undef W_G
-#undef W_GR
-#undef W_GD
-#endif
-}
-
-template <bool TB, int SIDE>
-__global__ __launch_bounds__(NTW) void gemm256w_kernel(GemmP p) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE2];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int nk = p.K / 64;
-    const bf16* A = reinterpret_cast<const bf16*>(p.A);
-    const bf16* B = reinterpret_cast<const bf16*>(p.B);
-    const int xcd = blockIdx.x & 7, stride = gridDim.x >> 3;
-    const int q = ntiles >> 3, r = ntiles & 7;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int cnt = q + (xcd < r ? 1 : 0);
-    int li = blockIdx.x >> 3;
-    if (li >= cnt) return;
-    auto coords = [&](int l, int& m0, int& n0) {
-        int tm, tn;
-        tile_coords(base + l, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
-        m0 = tm * T2; n0 = tn * T2;
-    };
-    int m0, n0;
-    coords(li, m0, n0);
-    // the load cursor runs two K-tiles ahead of the multiply cursor; past the last tile it stays on the last K-tile (harmless re-reads
-    // keep the per-iteration count of LDS-DMA instructions, which the counted vmcnt relies on, constant)
-    int ll = li, lkt = 0;
-    const bf16* a_base = A + (int64_t)m0 * p.lda;                                 // first element of the cursor's tile rows / columns
-    const bf16* b_base = TB ? B + n0 : B + (int64_t)n0 * p.ldb;
-    auto a_src = [&]() { return a_base + lkt * 64; };
-    auto b_src = [&]() { return TB ? b_base + (int64_t)(lkt * 64) * p.ldb : b_base + lkt * 64; };
-    auto advance = [&]() {
-        if (lkt + 1 < nk) { ++lkt; return; }
-        if (ll + stride < cnt) {
-            ll += stride; lkt = 0;
-            int tm0, tn0;
-            coords(ll, tm0, tn0);
-            a_base = A + (int64_t)tm0 * p.lda;
-            b_base = TB ? B + tn0 : B + (int64_t)tn0 * p.ldb;
-        }
-    };
-    glds_w<TB>(a_src(), p.lda, b_src(), p.ldb, smem, wave, lane);
-    advance();
-    glds_w<TB>(a_src(), p.lda, b_src(), p.ldb, smem + STAGE2, wave, lane);
-    advance();
-    acc_claim();
-    acc_zero();
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");       // K-tile 0 has landed
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    bf16x8 fa0[8], fb0[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) fa0[i] = read_frag2<false>(smem, wm * 128 + i * 16, 0, lane);
-    if constexpr (!TB) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fb0[j] = read_frag2<false>(smem + 32768, wn * 128 + j * 16, 0, lane);
-        plain_fence(fa0); plain_fence(fb0);
-    } else {
-        TrFrag tb[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tb[j] = read_frag2a(smem + 32768, wn * 128 + j * 16, 0, lane);
-        plain_fence(fa0); tr_fence(tb);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fb0[j] = tr_assemble(tb[j]);
-    }
-    int ln = li + stride;
-    bool has_next = ln < cnt;
-    WDma<TB> dma;
-    dma.init(p.lda, p.ldb, wave, lane);
-    dma.set_src(a_src(), b_src());
-    bf16x8 sbuf[SIDE != 0 ? 16 : 1];
-    for (int g = 0, kt = 0;; ++g) {
-        char* cur = smem + (g & 1) * STAGE2;
-        const char* nxt = smem + ((g + 1) & 1) * STAGE2;
-        ktile_w<TB>(fa0, fb0, cur, nxt, dma, [&](const bf16*& an, const bf16*& bn) {
-            advance(); an = a_src(); bn = b_src();
-            if constexpr (SIDE != 0) {
-                // the rows the epilogue reads: requested behind this K-tile's counted wait, two K-tiles before the tile is done (a K-tile and a half to arrive)
-                if (kt == nk - 2) {
-#pragma unroll
-                    for (int n = 0; n < 16; ++n) sbuf[n] = side_load_w<SIDE>(p, m0 + wm * 128, n0 + wn * 128, lane, n);
-                }
-            }
-        }, wave, lane, wm, wn);
-        if (++kt < nk) continue;
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the last MFMAs' results are not readable before their passes are through (asm MFMAs: nobody pads this)
-        epilogue_w<SIDE>(p, m0 + wm * 128, n0 + wn * 128, lane, sbuf);
-        if (!has_next) break;
-        kt = 0;
-        li = ln; coords(li, m0, n0);
-        ln = li + stride;
-        has_next = ln < cnt;
-        acc_zero();
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // trailing re-reads must land before the LDS is released
-}
-
-
-// =====================================================================================================================
-// 256 x 128 x 64 tile, 256 threads (4 waves as 2(M) x 2(N), 128 x 64 per wave), ONE 48 KiB LDS stage filled by LDS-DMA,
-// three workgroups per CU: load/compute overlap and -- the point -- epilogue/compute overlap come from the co-resident
-// workgroups (independent waves, independent vmcnt), not from an in-kernel software pipeline.
-// =====================================================================================================================
-enum { SS_BM = 256, SS_BN = 128, SS_NT = 256, SS_ABYTES = 32768, SS_BBYTES = 16384 };
-
-template <bool KSTRIDED, int ROWS>      // ROWS = extent of the non-K dim of the tile (256 for A, 128 for B)
-__device__ __forceinline__ void glds_tile_ss(const bf16* __restrict__ ptr, int ld, int r0, int k0, char* lds, int wave, int lane) {
-    constexpr int NI = ROWS * 128 / 1024 / 4;          // 1-KiB instructions per wave (4 waves)
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        if constexpr (!KSTRIDED) {
-            const int r8 = (wave * NI + i) * 8;
-            const int row = r8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ (row & 7);
-            const bf16* src = ptr + (int64_t)(r0 + row) * ld + k0 + chunk * 8;
-            __builtin_amdgcn_global_load_lds((glb_void_ptr)src, (lds_void_ptr)(lds + r8 * 128), 16, 0, 0);
-        } else {
-            constexpr int RB = ROWS * 2;                 // bytes per k-row
-            constexpr int KPI = 1024 / RB;               // k-rows per instruction (2 for 256 cols, 4 for 128 cols)
-            const int kb = (wave * NI + i) * KPI;
-            const int k = kb + lane / (64 / KPI);
-            const int slot = lane % (64 / KPI);          // 16-byte slot inside the row
-            const int col = (((slot >> 1) ^ ks_f(k)) << 4) + (slot & 1) * 8;
-            const bf16* src = ptr + (int64_t)(k0 + k) * ld + r0 + col;
-            __builtin_amdgcn_global_load_lds((glb_void_ptr)src, (lds_void_ptr)(lds + kb * RB), 16, 0, 0);
-        }
-    }
-}
-
-template <bool KSTRIDED, int ROWS>
-__device__ __forceinline__ bf16x8 read_frag_ss(const char* lds, int base16, int ks, int lane) {
-    if constexpr (!KSTRIDED) {
-        int row = base16 + (lane & 15);
-        return *reinterpret_cast<const bf16x8*>(lds + off_kc2(row, ks * 4 + (lane >> 4)));
-    } else {
-        int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-        int k = ks * 32 + g * 8 + q;
-        int col = base16 + 4 * p;
-        typedef __attribute__((address_space(3))) bf16x4* lp;
-        constexpr int RB = ROWS * 2;
-        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(lds + k * RB + ((((col >> 4) ^ ks_f(k))) << 5) + (col & 15) * 2));
-        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(lds + (k + 4) * RB + ((((col >> 4) ^ ks_f(k + 4))) << 5) + (col & 15) * 2));
-        bf16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return r;
-    }
-}
-
-template <bool TA, bool TB, int OCC>
-__global__ __launch_bounds__(SS_NT, OCC) void gemm_ss_kernel(GemmP p) {
-    __shared__ __attribute__((aligned(16))) char smem[SS_ABYTES + SS_BBYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int t = xcd_remap(blockIdx.x, ntiles);
-    int tm, tn;
-    tile_coords(t, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
-    const int m0 = tm * SS_BM, n0 = tn * SS_BN;
-    const int z = blockIdx.y;
-    const int kbeg = z * p.k_per_split;
-    const int kend = min(p.K, kbeg + p.k_per_split);
-    const int nk = (kend - kbeg) / 64;
-    const bf16* A = reinterpret_cast<const bf16*>(p.A);
-    const bf16* B = reinterpret_cast<const bf16*>(p.B);
-    char* ldsA = smem;
-    char* ldsB = smem + SS_ABYTES;
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt > 0) __syncthreads();                         // every wave is done reading the previous K-tile
-        glds_tile_ss<TA, SS_BM>(A, p.lda, m0, kbeg + kt * 64, ldsA, wave, lane);
-        glds_tile_ss<TB, SS_BN>(B, p.ldb, n0, kbeg + kt * 64, ldsB, wave, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 fb[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = read_frag_ss<TB, SS_BN>(ldsB, wn * 64 + j * 16, ks, lane);
-#pragma unroll
-            for (int ih = 0; ih < 2; ++ih) {
-                bf16x8 fa[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) fa[i] = read_frag_ss<TA, SS_BM>(ldsA, wm * 128 + (ih * 4 + i) * 16, ks, lane);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[ih * 4 + i][j] = mfma16(fb[j], fa[i], acc[ih * 4 + i][j]);
-            }
-        }
-    }
-    if (p.epi_swap) { epilogue_swap<8>(p, acc, m0 + wm * 128, n0 + wn * 64, z, lane); return; }
-    __syncthreads();
-    epilogue_staged<8, 2>(p, acc, smem + wave * 12288, m0 + wm * 128, n0 + wn * 64, z, lane);
-}
-
-
 
 // C[i] = epilogue(sum_s ws[s][i])   (fixed summation order -> bitwise reproducible); the full fused epilogue is available
 // here too so that small-M, long-K GEMMs (the B*S = 64-row slot MLPs) can be split along K to fill the chip
@@ -1982,128 +44,6 @@ __global__ void splitk_reduce_kernel(GemmP p) {
     }
 }
 
-// =====================================================================================================================
-// Small-M GEMM (M <= 128 rows: the B*S slot rows of the aggregation block and the head), bf16, B in nn.Linear layout [N, K]:
-// C[M, N] = epilogue(A[M, K] W^T).  These products stream a weight matrix of a few MB once and do almost no arithmetic; through the 128 x 128
-// kernel they needed split-K to reach more than a handful of CUs, i.e. two launches (product + reduce, ~8 + 6.5 us in the step) for ~1 us of
-// memory traffic.  Here: one workgroup per 16 output columns (N / 16 workgroups: 48 ... 256), its four waves split K four ways, every operand
-// fragment is ONE 16-byte global load per lane straight into the MFMA operand registers (A rows and W rows are both k-contiguous: no LDS
-// staging), PD k-steps of loads in flight per wave; the waves' partial tiles meet in LDS in a fixed order (deterministic) and wave 0 applies
-// the epilogue of splitk_reduce_kernel (same arithmetic, same order).
-// =====================================================================================================================
-// TB: W is stored [K, N] (the dgrad twins of the same layers: dX = dY W with W in nn.Linear layout [out, in] = [K, N]).  A lane then cannot load its fragment -- eight
-// consecutive k of ONE column -- directly; the wave loads the [32 k][16 columns] block by rows (16 bytes per lane), drops it into a 1 KiB LDS block of its own and
-// reads it back with the transposing ds_read_b64_tr_b16 (LDS executes a wave's instructions in order: no barrier).  These products used to take the 128 x 128 kernel
-// plus a split-K reduce (two launches, 12-15 us in the step).
-template <int MT, int SM_PD = 4, bool TB = false>      // MT = 16-row tiles of the output per workgroup; SM_PD = k-steps of loads in flight per wave (a launch of these is a latency chain: K / (4 * 32 * SM_PD) round trips to memory)
-__global__ __launch_bounds__(256) void gemm_smallm_kernel(GemmP p) {
-    __shared__ __attribute__((aligned(16))) f32x4 red[3][MT][64];
-    __shared__ __attribute__((aligned(16))) char wstage[TB ? 4 : 1][TB ? 1024 : 16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lm = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * 16;
-    const int mbase = blockIdx.y * (16 * MT);                // (grid.y > 1: every MT row tiles their own workgroup -- the launch policy for few column groups)
-    const int kw = p.K / 4;                                  // this wave's share of K (a multiple of 32: host)
-    const int k0 = wave * kw;
-    const bf16* A = reinterpret_cast<const bf16*>(p.A);
-    const bf16* W = reinterpret_cast<const bf16*>(p.B);
-    const bf16* wrow = TB ? W + (int64_t)(k0 + (lane >> 1)) * p.ldb + n0 + 8 * (lane & 1)      // row k0 + lane / 2 of the block, its left or right eight columns
-                          : W + (int64_t)(n0 + lm) * p.ldb + k0 + 8 * g;
-    const bf16* arow[MT];
-    bool aok[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-        const int m = mbase + t * 16 + lm;
-        aok[t] = m < p.M;
-        arow[t] = A + (int64_t)(aok[t] ? m : 0) * p.lda + k0 + 8 * g;
-    }
-    f32x4 acc[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // what the epilogue reads is requested before the K loop (wave 0): these launches are latency chains, not bandwidth
-    const bf16* res = reinterpret_cast<const bf16*>(p.res);
-    const bf16* aux_in = reinterpret_cast<const bf16*>(p.aux_in);
-    const int n = n0 + 4 * g;                               // this lane's four output columns
-    f32x4 bias = f32x4{0.f, 0.f, 0.f, 0.f};
-    bf16x4 resv[MT], auxv[MT];
-    const bool dact = p.act == DEVIAS_ACT_DGELU || p.act == DEVIAS_ACT_DRELU;
-    if (wave == 0) {
-        if (p.bias) bias = *reinterpret_cast<const f32x4*>(p.bias + n);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const int m = mbase + t * 16 + lm;
-            if (res && m < p.M) resv[t] = *reinterpret_cast<const bf16x4*>(res + (int64_t)(p.res_mod > 0 ? m % p.res_mod : m) * p.ldr + n);
-            if (dact && m < p.M) auxv[t] = *reinterpret_cast<const bf16x4*>(aux_in + (int64_t)m * p.ld_aux + n);
-        }
-    }
-    const int nks = kw / 32;
-    bf16x8 fb[SM_PD], fa[SM_PD][MT];
-    auto issue = [&](int slot, int ks) {
-        fb[slot] = *reinterpret_cast<const bf16x8*>(wrow + (TB ? (int64_t)ks * 32 * p.ldb : (int64_t)ks * 32));
-#pragma unroll
-        for (int t = 0; t < MT; ++t) fa[slot][t] = *reinterpret_cast<const bf16x8*>(arow[t] + ks * 32);
-    };
-#pragma unroll
-    for (int d = 0; d < SM_PD; ++d) if (d < nks) issue(d, d);
-    for (int ks0 = 0; ks0 < nks; ks0 += SM_PD) {
-#pragma unroll
-        for (int d = 0; d < SM_PD; ++d) {
-            const int ks = ks0 + d;
-            if (ks < nks) {
-                bf16x8 wf = fb[d];
-                if constexpr (TB) {          // rows -> this lane's column: through the wave's LDS block
-                    char* blk = wstage[wave];
-                    *reinterpret_cast<bf16x8*>(blk + lane * 16) = fb[d];
-                    typedef __attribute__((address_space(3))) bf16x4* lp;
-                    const int q = lm >> 2, pp = lm & 3;
-                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(blk + (8 * g + q) * 32 + 8 * pp));
-                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lp)(blk + (8 * g + q + 4) * 32 + 8 * pp));
-                    wf = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-#pragma unroll
-                for (int t = 0; t < MT; ++t) acc[t] = mfma16(wf, fa[d][t], acc[t]);
-                if (ks + SM_PD < nks) issue(d, ks + SM_PD);
-            }
-        }
-    }
-    // rows beyond M were computed from row 0's data: they are never stored.  Partial tiles of waves 1..3 -> LDS; wave 0 adds them in that order
-    if (wave > 0) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t) red[wave - 1][t][lane] = acc[t];
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    bf16* aux_out = reinterpret_cast<bf16*>(p.aux_out);
-    bf16* C = reinterpret_cast<bf16*>(p.C);
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-        const int m = mbase + t * 16 + lm;
-        f32x4 v = acc[t];
-#pragma unroll
-        for (int w = 0; w < 3; ++w) v += red[w][t][lane];
-        if (m >= p.M) continue;
-        if (p.bias) v += bias;
-        if (p.act == DEVIAS_ACT_GELU) {
-            if (aux_out) store4(aux_out + (int64_t)m * p.ld_aux + n, v);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_t<bf16>(v[e]);
-        } else if (p.act == DEVIAS_ACT_RELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        } else if (p.act == DEVIAS_ACT_SIGMOID) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = 1.0f / (1.0f + expf(-v[e]));
-        } else if (dact) {
-            const f32x4 a4 = {(float)auxv[t][0], (float)auxv[t][1], (float)auxv[t][2], (float)auxv[t][3]};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = p.act == DEVIAS_ACT_DGELU ? v[e] * dgelu_t<bf16>(a4[e]) : (a4[e] > 0.f ? v[e] : 0.f);
-        }
-        if (p.row_scale) v *= p.row_scale[m / p.rows_per_scale];
-        if (res) v += f32x4{(float)resv[t][0], (float)resv[t][1], (float)resv[t][2], (float)resv[t][3]};
-        store4(C + (int64_t)m * p.ldc + n, v);
-    }
-}
-
 // the weight-gradient case of the reduce (fp32 C with ldc == N, no epilogue beyond beta): 16 bytes per lane, no per-element div/mod
 __global__ __launch_bounds__(256) void splitk_reduce_plain_kernel(const float* __restrict__ ws, int split_k, int64_t total4, float* __restrict__ C, float beta) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
@@ -2129,16 +69,6 @@ __global__ void gemm_colsum_final_kernel(const float* __restrict__ part, int npa
         for (int k = 0; k < 16; ++k) t += sm[k][threadIdx.x];
         out[n] = t + (beta != 0.f ? beta * out[n] : 0.f);
     }
-}
-
-template <typename T, bool VEC>
-int launch(const GemmP& p, int ta, int tb, hipStream_t st, int batch = 1) {
-    dim3 grid(p.tiles_m * p.tiles_n, p.split_k, batch), block(NTHREADS);
-    if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<T, false, false, VEC>), grid, block, 0, st, p);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<T, false, true, VEC>), grid, block, 0, st, p);
-    else if (ta && tb) hipLaunchKernelGGL((gemm_kernel<T, true, true, VEC>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((gemm_kernel<T, true, false, VEC>), grid, block, 0, st, p);
-    return 0;
 }
 
 }  // namespace
@@ -2197,35 +127,9 @@ extern "C" int32_t devias_policy_gemm_cus(void) {
     return (ncu - reserve > 8 ? ncu - reserve : 8) & ~7;
 }
 
-// The eight-wave persistent kernel's instantiation for a call: operand layout, the rows its epilogue reads (SIDE), static lists or dynamic queues, and -- option
-// gemm_epi_spec, on by default -- the epilogue's switches as compile-time facts (EPI, see epilogue_swap) where the call's combination has an instantiation:
-// the encoder block's seven (qkv: bias; fc1: bias + GELU + saved pre-activation; proj / fc2 / patch embedding: bias + residual; and, on TRANSPOSED weight copies
-// (devias_block_args.W*T: the dgrad GEMMs then read both operands k-contiguous, 9-17 % less K-loop time than with transposing LDS reads), dfc1 / dqkv: nothing; dproj: column
-// sums; dfc2: dGELU + column sums).  Everything else (stochastic depth's row scale, ReLU / Sigmoid heads, B k-strided ...) runs the generic form.
-namespace {
-template <bool TB, int SIDE, bool DYN, int EPI>
-void pers_launch1(dim3 grid, hipStream_t st, const GemmP& p) { hipLaunchKernelGGL((gemm256p_kernel<TB, SIDE, DYN, EPI>), grid, dim3(NT2), 0, st, p); }
-template <bool DYN>
-void pers_launch(bool tb, int side, int epi, dim3 grid, hipStream_t st, const GemmP& p) {
-    if (!tb && side == 0) {
-        if (epi == EPI_BIAS) pers_launch1<false, 0, DYN, EPI_BIAS>(grid, st, p);                                                                        // qkv
-        else if (epi == (DEVIAS_ACT_GELU | EPI_BIAS | EPI_AUX)) pers_launch1<false, 0, DYN, DEVIAS_ACT_GELU | EPI_BIAS | EPI_AUX>(grid, st, p);         // fc1
-        else if (epi == 0) pers_launch1<false, 0, DYN, 0>(grid, st, p);                                                                                 // dfc1, dqkv on a transposed weight copy
-        else if (epi == EPI_CS) pers_launch1<false, 0, DYN, EPI_CS>(grid, st, p);                                                                       // dproj
-        else pers_launch1<false, 0, DYN, -1>(grid, st, p);
-    } else if (!tb && side == 1) {
-        if (epi == EPI_BIAS) pers_launch1<false, 1, DYN, EPI_BIAS>(grid, st, p);                                                                        // proj, fc2, patch embedding
-        else pers_launch1<false, 1, DYN, -1>(grid, st, p);
-    } else if (!tb) {
-        if (epi == (DEVIAS_ACT_DGELU | EPI_CS)) pers_launch1<false, 2, DYN, DEVIAS_ACT_DGELU | EPI_CS>(grid, st, p);                                     // dfc2 on a transposed weight copy
-        else pers_launch1<false, 2, DYN, -1>(grid, st, p);
-    } else if (side == 0) pers_launch1<true, 0, DYN, -1>(grid, st, p);       // B k-strided (a dgrad without a transposed weight copy: hosts of ABI <= 165, the per-kernel path): generic epilogues
-    else pers_launch1<true, 2, DYN, -1>(grid, st, p);
-}
-}  // namespace
-
 static int gemm_impl(const devias_gemm_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    // ---- 1. validate, fill GemmP -----------------------------------------------------------------------------------------------------------
     DEVIAS_REQUIRE(a && a->A && a->B && a->C, "devias_gemm: null operand");
     DEVIAS_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, "devias_gemm: bad dims M=%d N=%d K=%d", a->M, a->N, a->K);
     DEVIAS_REQUIRE(a->dtype == DEVIAS_F32 || a->dtype == DEVIAS_BF16, "devias_gemm: bad dtype %d", a->dtype);
@@ -2276,6 +180,9 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
     if (batch > 1)
         DEVIAS_REQUIRE(split == 1 && !a->colsum && !a->res && !a->aux_in && !a->aux_out && batch <= 65535,
                        "devias_gemm: batched launches support bias / activation epilogues only (no split-K, residual, aux, colsum)");
+    if (a->colsum)
+        DEVIAS_REQUIRE(split == 1 && a->ws && !(a->c_f32 && a->dtype == DEVIAS_BF16),
+                       "devias_gemm: colsum needs split_k == 1, a workspace (M/128 * N floats) and a T-typed C");
     p.debug = opt[OPT_GEMM_DEBUG];
     p.tail_split = opt[OPT_GEMM_TAIL_SPLIT];
     p.aux_nt = opt[OPT_GEMM_AUX_NT];
@@ -2288,89 +195,59 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
     // rasterisation (measured, tools/gemm_ablate.py): wide outputs (N >= 2048) gain 7-10 % from 8-row-tile groups (the
     // weight panel set of a group stays in the XCD's L2); narrow ones and the wgrad reductions are best n-fastest
     p.group_m = opt[OPT_GEMM_GROUPM] > 0 ? opt[OPT_GEMM_GROUPM] : ((!a->trans_a && a->N >= 2048) ? 8 : 1);
-
     // 16 bytes per lane in the staged epilogue (8 bf16 / 2 x 4 fp32): leading dims % 8 and 16-byte aligned bases
     const bool v16 = vc && (a->N % 8 == 0) && (a->ldc % 8 == 0) && aligned16(a->C) && (!a->bias || aligned16(a->bias)) &&
                      (!a->res || ((a->ldr % 8 == 0) && aligned16(a->res))) &&
                      (!a->aux_in || ((a->ld_aux % 8 == 0) && aligned16(a->aux_in))) &&
                      (!a->aux_out || ((a->ld_aux % 8 == 0) && aligned16(a->aux_out))) && (split == 1 || aligned16(a->ws));
     p.vec16 = (v16 && a->dtype == DEVIAS_BF16) ? 1 : 0;
-    bool big = opt[OPT_GEMM256] && a->dtype == DEVIAS_BF16 && vec && vc && (a->M % T2 == 0) && (a->N % T2 == 0) && (a->K % 64 == 0) &&
-               (p.k_per_split % 64 == 0);
-    big = big && v16 && batch == 1;
-    // Kernel choice, measured on MI355X at the ViT-B shapes (M = 50176; tools/gemm_block_shapes.py, tools/ab_bench.py):
+
+    // ---- 2. choose the kernel family and its form ------------------------------------------------------------------------------------------
+    // Measured on MI355X at the ViT-B shapes (M = 50176; tools/gemm_block_shapes.py, tools/ab_bench.py):
     //   * 256x256 two-stage LDS-DMA kernel (1 workgroup/CU): every shape it can tile, all four operand layouts; its persistent form
     //     (gemm256p_kernel) when there is more than one round of tiles, no split-K and a bf16 output (forward and dgrad GEMMs);
     //   * 256x128 single-stage kernel (2 workgroups/CU): N a multiple of 128 but not of 256;
     //   * 128x128 register-staged kernel: ragged / unaligned / fp32 shapes.
+    const int ta = a->trans_a, tb = a->trans_b;
+    bool big = opt[OPT_GEMM256] && a->dtype == DEVIAS_BF16 && vec && vc && (a->M % T2 == 0) && (a->N % T2 == 0) && (a->K % 64 == 0) &&
+               (p.k_per_split % 64 == 0) && v16 && batch == 1;
     bool ss = opt[OPT_GEMM_SS] != 0 && a->dtype == DEVIAS_BF16 && vec && v16 && (a->M % SS_BM == 0) && (a->N % SS_BN == 0) && (a->K % 64 == 0) &&
-              (p.k_per_split % 64 == 0) && batch == 1 && !(a->trans_a && !a->trans_b);      // (A k-strided with B k-contiguous: no caller; that
-                                                                                             //  instantiation spilled registers and was removed)
-    if (ss && big) {
-        const bool nt = !a->trans_a && !a->trans_b;
-        if (opt[OPT_GEMM_SS] < 0 || nt) ss = false;
-    }
-    // small-M products (the aggregation block's and the head's B*S-row GEMMs): one launch, no split-K (gemm_smallm_kernel)
-    const bool smallm = opt[OPT_GEMM_SMALLM] && a->dtype == DEVIAS_BF16 && !a->trans_a && (!a->trans_b || opt[OPT_GEMM_SMALLM] == 1) && a->M <= 128 && batch == 1 && !p.c_f32 && !a->colsum && vec && vc &&
+              (p.k_per_split % 64 == 0) && batch == 1 && !(ta && !tb);      // (A k-strided with B k-contiguous: no caller; that
+                                                                            //  instantiation spilled registers and was removed)
+    if (ss && big && (opt[OPT_GEMM_SS] < 0 || (!ta && !tb))) ss = false;
+    if (ss) big = false;
+    // small-M products (the aggregation block's and the head's B*S-row GEMMs): one launch, no split-K (gemm_smallm_kernel); chosen before the tiled families
+    const bool smallm = opt[OPT_GEMM_SMALLM] && a->dtype == DEVIAS_BF16 && !ta && (!tb || opt[OPT_GEMM_SMALLM] == 1) && a->M <= 128 && batch == 1 && !p.c_f32 && !a->colsum && vec && vc &&
                         (a->N % 16 == 0) && (a->K % 128 == 0) && (a->lda % 8 == 0) && (a->ldb % 8 == 0) && (a->ldc % 4 == 0) && aligned8(a->C) &&
                         (!a->bias || aligned16(a->bias)) && (!a->res || (a->ldr % 4 == 0 && aligned8(a->res))) &&
                         (!a->aux_in || (a->ld_aux % 4 == 0 && aligned8(a->aux_in))) && (!a->aux_out || (a->ld_aux % 4 == 0 && aligned8(a->aux_out)));
-    if (smallm) {
-        p.split_k = 1; p.k_per_split = a->K;
-        const int mt = cdiv(a->M, 16);
-        dim3 grid(a->N / 16), block(256);
-        // few column groups (N = 768: 48 workgroups on 256 CUs, each streaming all M rows of A over a long K): one workgroup per 16-row tile as well -- the same
-        // arithmetic in the same order per output element (bitwise equal), four times the workgroups, a quarter of the A bytes per workgroup.  In the step
-        // (R = 64 rows, K = 3072, N = 768: the slot MLP's second layer and the composite output projection; 16 launches of 17.5 us per step):
-        // -0.13 ms with the split alone, -0.25 ms with twelve instead of four k-steps of loads in flight per wave (a wave's 24 k-steps are then two round trips to
-        // memory instead of six) -- tools/ab_inproc.py gemm_smallm=2,1
-        if (a->trans_b) { grid = dim3(a->N / 16, mt); hipLaunchKernelGGL((gemm_smallm_kernel<1, 12, true>), grid, block, 0, st, p); }      // W stored [K, N]: always a workgroup per row tile
-        else if (opt[OPT_GEMM_SMALLM] == 1 && mt > 1 && a->N / 16 < 128) { grid = dim3(a->N / 16, mt); hipLaunchKernelGGL((gemm_smallm_kernel<1, 12>), grid, block, 0, st, p); }
-        else
-        if (mt <= 1) hipLaunchKernelGGL((gemm_smallm_kernel<1, 12>), grid, block, 0, st, p);
-        else if (mt <= 2) hipLaunchKernelGGL((gemm_smallm_kernel<2>), grid, block, 0, st, p);
-        else if (mt <= 4) hipLaunchKernelGGL((gemm_smallm_kernel<4>), grid, block, 0, st, p);      // (all six k-steps of a K = 768 wave in flight, <4, 6>: no gain in the step)
-        else if (mt <= 6) hipLaunchKernelGGL((gemm_smallm_kernel<6>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_smallm_kernel<8>), grid, block, 0, st, p);
-        devias_count(DEVIAS_CNT_GEMM_SMALLM);
-        DEVIAS_CHECK_LAUNCH("devias_gemm(small M)");
-        return DEVIAS_OK;
-    }
-    bool colsum_fused = false;
-    if (a->colsum) {
-        DEVIAS_REQUIRE(split == 1 && a->ws && !(a->c_f32 && a->dtype == DEVIAS_BF16),
-                       "devias_gemm: colsum needs split_k == 1, a workspace (M/128 * N floats) and a T-typed C");
-        if (ss || big) { p.colsum_part = a->ws; colsum_fused = true; }      // the full-tile kernels fold it into their epilogue
-    }
-    if (ss) {
-        p.tiles_m = a->M / SS_BM; p.tiles_n = a->N / SS_BN;
-        dim3 grid(p.tiles_m * p.tiles_n, p.split_k), block(SS_NT);
-        const int ta = a->trans_a, tb = a->trans_b;
-        if (!ta && !tb) hipLaunchKernelGGL((gemm_ss_kernel<false, false, 2>), grid, block, 0, st, p);
-        else if (!ta && tb) hipLaunchKernelGGL((gemm_ss_kernel<false, true, 2>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_ss_kernel<true, true, 2>), grid, block, 0, st, p);
-        devias_count(DEVIAS_CNT_GEMM_SS);
-    } else if (big) {
-        p.tiles_m = a->M / T2; p.tiles_n = a->N / T2;
-        const int ta = a->trans_a, tb = a->trans_b;
-        const int nt = p.tiles_m * p.tiles_n;
-        // grid of the persistent forms: one workgroup per CU the policy counts on.  With the dynamic queues a reserve is pointless for THEM (a workgroup that
-        // finds no CU pulls nothing): they launch on every CU, and gemm_reserve_cus then only sizes the weight-gradient split-K (one round of the CUs left)
-        // gemm_dynamic (profiles/r4_cu_hog.txt): the queues are robust to CUs held or slowed by a concurrent kernel, -2.5 ms per step with 16 CUs held during backward; the static
-        // lists are 0.3 ms per step faster when the GPU is the step's alone -- hence -1 (default): queues exactly when the host has announced concurrent kernels (gemm_concurrent)
-        const bool dyn = opt[OPT_GEMM_DYNAMIC] > 0 || (opt[OPT_GEMM_DYNAMIC] < 0 && opt[OPT_GEMM_CONCURRENT] != 0);      // (round 6: queues only for fc1, or fc1 + dfc2 -- the launches whose tiles vary most --: -0.09 / -0.03 / -0.04 ms, noise)
-        const int gp = dyn ? (devias_device_cus() & ~7) : devias_policy_gemm_cus();
+    // few column groups (N = 768: 48 workgroups on 256 CUs, each streaming all M rows of A over a long K): one workgroup per 16-row tile as well -- the same
+    // arithmetic in the same order per output element (bitwise equal), four times the workgroups, a quarter of the A bytes per workgroup.  In the step
+    // (R = 64 rows, K = 3072, N = 768: the slot MLP's second layer and the composite output projection; 16 launches of 17.5 us per step):
+    // -0.13 ms with the split alone, -0.25 ms with twelve instead of four k-steps of loads in flight per wave (a wave's 24 k-steps are then two round trips to
+    // memory instead of six) -- tools/ab_inproc.py gemm_smallm=2,1.  W stored [K, N]: always a workgroup per row tile (the launcher)
+    const bool smallm_row_tiles = opt[OPT_GEMM_SMALLM] == 1 && a->M > 16 && a->N / 16 < 128;
+    const bool colsum_fused = a->colsum && (ss || big);      // the full-tile kernels fold the column sums into their epilogue
+    if (colsum_fused) p.colsum_part = a->ws;
+    // The 256x256 family's forms.  Grid of the persistent ones: one workgroup per CU the policy counts on.  With the dynamic queues a reserve is pointless for THEM
+    // (a workgroup that finds no CU pulls nothing): they launch on every CU, and gemm_reserve_cus then only sizes the weight-gradient split-K (one round of the CUs left)
+    // gemm_dynamic (profiles/r4_cu_hog.txt): the queues are robust to CUs held or slowed by a concurrent kernel, -2.5 ms per step with 16 CUs held during backward; the static
+    // lists are 0.3 ms per step faster when the GPU is the step's alone -- hence -1 (default): queues exactly when the host has announced concurrent kernels (gemm_concurrent)
+    const int nt = (a->M / T2) * (a->N / T2);
+    bool dyn = false, pers = false, w4_ok = false;
+    int gp = 0, side = 0;
+    if (big && !smallm) {
+        dyn = opt[OPT_GEMM_DYNAMIC] > 0 || (opt[OPT_GEMM_DYNAMIC] < 0 && opt[OPT_GEMM_CONCURRENT] != 0);      // (round 6: queues only for fc1, or fc1 + dfc2 -- the launches whose tiles vary most --: -0.09 / -0.03 / -0.04 ms, noise)
+        gp = dyn ? (devias_device_cus() & ~7) : devias_policy_gemm_cus();
         // persistent form (more than one round of tiles, no split-K, bf16 output): measured per shape at M = 50176 (tools/gemm_block_shapes.py, same
         // box, one-tile-per-workgroup -> persistent): qkv 226 -> 204 us, fc1 278 -> 243, dfc2 + dGELU + colsum 415 -> 349, dfc2 plain 275 -> 248,
         // dproj 81 -> 72; the long-K dgrad shapes unchanged (dfc1 252, dqkv 192)
         const bool dact = a->act == DEVIAS_ACT_DGELU || a->act == DEVIAS_ACT_DRELU;
-        const int side = a->res ? 1 : (dact ? 2 : 0);      // rows the epilogue reads: a compile-time fact of the persistent kernels
+        side = a->res ? 1 : (dact ? 2 : 0);      // rows the epilogue reads: a compile-time fact of the persistent kernels
         const bool pers_ok = !ta && split == 1 && !p.c_f32 && p.epi_swap && gp >= 8 && !(a->res && dact) && !(tb && side == 1) &&
                              (!a->row_scale || p.rows_per_scale >= 128) && !(side == 2 && a->bias) && !(side == 1 && a->colsum) &&
                              !(side != 0 && a->aux_out);
-#define PERS_LAUNCH(KERNEL, ...) do { \
-            if (!tb) { if (side == 0) hipLaunchKernelGGL((KERNEL<false, 0 __VA_ARGS__>), grid, block, 0, st, p); else hipLaunchKernelGGL((KERNEL<false, 1 __VA_ARGS__>), grid, block, 0, st, p); } \
-            else { if (side == 0) hipLaunchKernelGGL((KERNEL<true, 0 __VA_ARGS__>), grid, block, 0, st, p); else hipLaunchKernelGGL((KERNEL<true, 2 __VA_ARGS__>), grid, block, 0, st, p); } } while (0)
+        pers = opt[OPT_GEMM_PERSISTENT] && pers_ok && nt > gp;
         // Four-wave form (gemm256w_kernel).  gemm_w4 is a mask over its four instantiations: 1 = B k-contiguous, no side rows; 2 = B k-contiguous + residual;
         // 4 = B k-strided, no side rows; 8 = B k-strided + saved pre-activation; -1 (default) = the measured policy (rounds 4-5: all four where K >= 1024 and N >= 1024 -- every GEMM of ViT-L, none of ViT-B; since round 6: none, below).  Measured IN the step, one process,
         // the option toggled between blocks of ten steps (tools/ab_inproc.py, profiles/r4_dormant_kernels.txt): ViT-L/16 16x224^2 (K = 1024 / 4096) -3.0 ms of
@@ -2385,55 +262,61 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
         // process (tools/ab_inproc.py --model vit_large gemm_w4=-1,0, the old policy "all four where K >= 1024 and N >= 1024" against none): -0.84 / -0.52 ms of 137.2; forms 1 / 2
         // alone against none +0.22 / -0.01 (profiles/r6_side_configs.txt).  Its N = 1024 shapes have 3.06 rounds of tiles and the four-wave kernel has no tail split.
         const int w4_mask = opt[OPT_GEMM_W4] >= 0 ? opt[OPT_GEMM_W4] : 0;
-        const bool w4_ok = opt[OPT_GEMM_PERSISTENT] && !dyn && ((w4_mask >> w4_form) & 1) && pers_ok && !(!tb && side == 2) && nt > gp && a->K >= 128 &&      // (B k-contiguous + saved pre-activation -- dfc2 on a transposed weight copy -- has no four-wave form)
-                           (a->act == DEVIAS_ACT_NONE || a->act == DEVIAS_ACT_GELU || a->act == DEVIAS_ACT_DGELU || a->act == DEVIAS_ACT_DRELU);
+        w4_ok = pers && !dyn && ((w4_mask >> w4_form) & 1) && !(!tb && side == 2) && a->K >= 128 &&      // (B k-contiguous + saved pre-activation -- dfc2 on a transposed weight copy -- has no four-wave form)
+                (a->act == DEVIAS_ACT_NONE || a->act == DEVIAS_ACT_GELU || a->act == DEVIAS_ACT_DGELU || a->act == DEVIAS_ACT_DRELU);
+    }
+    // the persistent eight-wave kernel's instantiation (launch_gemm256p): the epilogue's switches of this call (EPI of epilogue_swap, option gemm_epi_spec, on by default);
+    // -1 = the generic form
+    const int epi = !opt[OPT_GEMM_EPI_SPEC] ? -1 : (a->act | (a->bias ? EPI_BIAS : 0) | (a->aux_out ? EPI_AUX : 0) | (a->row_scale ? EPI_RS : 0) | (p.colsum_part ? EPI_CS : 0));
+
+    // ---- 3. launch ------------------------------------------------------------------------------------------------------------------------
+    if (smallm) {
+        p.split_k = 1; p.k_per_split = a->K;
+        launch_gemm_smallm(p, tb != 0, smallm_row_tiles, st);
+        devias_count(DEVIAS_CNT_GEMM_SMALLM);
+        DEVIAS_CHECK_LAUNCH("devias_gemm(small M)");
+        return DEVIAS_OK;
+    }
+    if (ss) {
+        p.tiles_m = a->M / SS_BM; p.tiles_n = a->N / SS_BN;
+        launch_gemm_ss(p, ta, tb, st);
+        devias_count(DEVIAS_CNT_GEMM_SS);
+    } else if (big) {
+        p.tiles_m = a->M / T2; p.tiles_n = a->N / T2;
         if (w4_ok) {
-            dim3 grid(gp), block(NTW);
-            PERS_LAUNCH(gemm256w_kernel);
+            launch_gemm256w(p, tb != 0, side, gp, st);
             devias_count(DEVIAS_CNT_GEMM256P);
             devias_count(DEVIAS_CNT_GEMM256W);
-        } else if (opt[OPT_GEMM_PERSISTENT] && pers_ok && nt > gp) {
-            dim3 grid(gp);
-            // the epilogue's switches of this call (EPI of epilogue_swap); -1 = the generic instantiation
-            const int epi = !opt[OPT_GEMM_EPI_SPEC] ? -1 : (a->act | (a->bias ? EPI_BIAS : 0) | (a->aux_out ? EPI_AUX : 0) | (a->row_scale ? EPI_RS : 0) | (p.colsum_part ? EPI_CS : 0));
+        } else if (pers) {
             // dynamic queue: every XCD queue has at least one (reserved) item per workgroup, at most 32 workgroups per XCD (one claim-mask word)
             unsigned int *tq = nullptr, *tq_clear = nullptr;
-            if (!(dyn && a->K >= 128 && (gp >> 3) <= 32 && (nt >> 3) >= (gp >> 3) && tile_queue_slot(st, &tq, &tq_clear))) tq = nullptr;
-            if (tq) {
-                // dynamic tile queue (default): the item list of an XCD queue of cnt tiles -- whole tiles, then the halves of a split partial round --
-                // for the two queue lengths that occur; this launch's ring slot and the one it zeroes (both from the ring of this device AND this stream)
+            if (dyn && a->K >= 128 && (gp >> 3) <= 32 && (nt >> 3) >= (gp >> 3) && tile_queue_slot(st, &tq, &tq_clear)) {
+                // the item list of an XCD queue of cnt tiles -- whole tiles, then the halves of a split partial round -- for the two queue lengths that
+                // occur; this launch's ring slot and the one it zeroes (both from the ring of this device AND this stream)
                 p.tq = tq;
                 p.tq_clear = tq_clear;
                 const int stride = gp >> 3;
                 for (int v = 0; v < 2; ++v) {
                     const int cnt = (nt >> 3) + (v == 0 ? 1 : 0);
                     const int rfull = cnt / stride, rem = cnt - rfull * stride;
-                    const bool split = opt[OPT_GEMM_TAIL_SPLIT] != 0 && rfull >= 1 && rem > 0 && 2 * rem <= stride;
-                    p.tq_nwhole[v] = split ? rfull * stride : cnt;
-                    p.tq_items[v] = split ? rfull * stride + 2 * rem : cnt;
+                    const bool tail = opt[OPT_GEMM_TAIL_SPLIT] != 0 && rfull >= 1 && rem > 0 && 2 * rem <= stride;
+                    p.tq_nwhole[v] = tail ? rfull * stride : cnt;
+                    p.tq_items[v] = tail ? rfull * stride + 2 * rem : cnt;
                 }
-                pers_launch<true>(tb != 0, side, epi, grid, st, p);
                 devias_count(DEVIAS_CNT_GEMM256D);
-            } else {
-                pers_launch<false>(tb != 0, side, epi, grid, st, p);
             }
+            if (p.tq) launch_gemm256p_dyn(p, tb != 0, side, epi, gp, st);
+            else launch_gemm256p(p, tb != 0, side, epi, gp, st);
             devias_count(DEVIAS_CNT_GEMM256P);
         } else {
-            dim3 grid(nt, p.split_k), block(NT2);
-            if (p.split_k > 1 && opt[OPT_GEMM_SPLITK_XCD]) grid = dim3(8 * ((nt * p.split_k + 7) / 8));      // (slab, tile) pairs in XCD-major order (gemm256_kernel)
-            if (!ta && !tb) hipLaunchKernelGGL((gemm256_kernel<false, false, 1>), grid, block, 0, st, p);
-            else if (!ta && tb) hipLaunchKernelGGL((gemm256_kernel<false, true>), grid, block, 0, st, p);
-            else if (ta && tb) hipLaunchKernelGGL((gemm256_kernel<true, true>), grid, block, 0, st, p);
-            else hipLaunchKernelGGL((gemm256_kernel<true, false>), grid, block, 0, st, p);
+            launch_gemm256(p, ta, tb, opt[OPT_GEMM_SPLITK_XCD] != 0, st);
             devias_count(DEVIAS_CNT_GEMM256);
         }
     } else if (a->dtype == DEVIAS_BF16) {
-        if (vec) launch<bf16, true>(p, a->trans_a, a->trans_b, st, batch);
-        else launch<bf16, false>(p, a->trans_a, a->trans_b, st, batch);
+        launch_gemm128_bf16(p, vec, ta, tb, batch, st);
         devias_count(DEVIAS_CNT_GEMM128_BF16);
     } else {
-        if (vec) launch<float, true>(p, a->trans_a, a->trans_b, st, batch);
-        else launch<float, false>(p, a->trans_a, a->trans_b, st, batch);
+        launch_gemm128_f32(p, vec, ta, tb, batch, st);
         devias_count(DEVIAS_CNT_GEMM128_F32);
     }
     DEVIAS_CHECK_LAUNCH("devias_gemm");

@@ -1,4 +1,4 @@
-"""Audit of the compiled four-wave GEMM kernels (gemm256w_kernel, devias_amd/csrc/gemm.hip).  Their 256 accumulator registers are AGPRs named
+"""Audit of the compiled four-wave GEMM kernels (gemm256w_kernel, devias_amd/csrc/gemm256w.hip).  Their 256 accumulator registers are AGPRs named
 LITERALLY in inline asm: the compiler does not know they are live, so the kernels are correct only if the compiler itself touches no AGPR and
 spills nothing (a spill would go through the AGPR half or scratch).  This test compiles the device code with the production flags and checks
 exactly that in the ISA, for every instantiation.  CPU only: hipcc cross-compiles gfx950 without a GPU."""
@@ -16,7 +16,10 @@ _ISA = {}
 
 
 def _isa(stem, extra=()):
-    """the gfx950 ISA of one translation unit under the production flags (+ extra), compiled once per session: gemm.hip takes over a minute"""
+    """the gfx950 ISA of one translation unit under the production flags (+ extra), compiled once per session; stem "gemm*" = every GEMM unit
+    (build.GEMM_SOURCES: the kernel families' units + the host side), concatenated"""
+    if stem == "gemm*":
+        return "\n".join(_isa(s[:-len(".hip")], extra) for s in build.GEMM_SOURCES)
     key = (stem, tuple(extra))
     if key not in _ISA:
         src = os.path.join(ROOT, "devias_amd", "csrc", stem + ".hip")
@@ -30,7 +33,7 @@ def _isa(stem, extra=()):
 
 @pytest.mark.timeout(900)
 def test_four_wave_gemm_kernels_own_their_accumulators():
-    lines = _isa("gemm").split("\n")
+    lines = _isa("gemm*").split("\n")
     found = 0
     for i, l in enumerate(lines):
         m = re.match(r"^(_ZN\S*gemm256w_kernel\S*):", l)
@@ -67,7 +70,7 @@ def test_eight_wave_persistent_gemm_kernels_do_not_spill():
     specialised epilogues with column sums (EPI_CS) spilled 52-132 bytes -- with no branch left between the sixteen pieces the compiler sank all 128 column-sum adds
     behind the last piece and kept every piece alive for them.  Every instantiation -- <B layout, side rows, static / dynamic, generic / specialised epilogue> --
     must therefore have no scratch, exactly the MFMAs of its K-tile bodies, and every specialisation the host dispatches to must exist."""
-    text = _isa("gemm")
+    text = _isa("gemm*")
     sizes = dict(re.findall(r"\.set (\S*gemm256p_kernel\S*)\.private_seg_size, (\d+)", text))
     assert len(sizes) == 22, sorted(sizes)       # 2 (dynamic) x [ (F,0): generic, bias, bias+GELU+aux, none, colsum | (F,1): generic, bias | (F,2): generic, dGELU+colsum | (T,0): generic | (T,2): generic ]
     assert all(int(v) == 0 for v in sizes.values()), {k[-34:]: v for k, v in sizes.items() if int(v)}
@@ -105,13 +108,13 @@ def test_inline_asm_vmem_never_reads_an_sgpr_the_valu_just_wrote():
     reloads a spilled SGPR from a lane of its spill VGPR) needs 5 wait states.  The compiler's hazard recogniser inserts them for its own
     instructions but not inside inline asm, and this library issues stores and atomics from inline asm with an SGPR-pair base (the deferred epilogue
     stores, the stream-K partials, the dynamic tile queue's dequeues).  Round 4 found the failure mode on the GPU: a dequeue whose slot pointer had just
-    come out of a spill lane went to an address with a stale high half (memory fault).  This audit walks the ISA of gemm.hip -- release and
+    come out of a spill lane went to an address with a stale high half (memory fault).  This audit walks the ISA of every GEMM unit -- release and
     -DDEVIAS_GEMM_DEBUG builds -- and requires, for every inline-asm vector-memory instruction with an SGPR base, that none of the 5 issue slots before it
     (s_nop N counts N + 1) holds a VALU write of that SGPR."""
     vmem = re.compile(r"^\s*(global_(?:store|load|atomic)\w*|buffer_\w+)\s+(.*)$")
     valu_sgpr_write = re.compile(r"^\s*(v_readlane_b32|v_readfirstlane_b32)\s+s(\d+)\b")
     for extra in ([], ["-DDEVIAS_GEMM_DEBUG"]):
-        lines = [l.split(";")[0].rstrip() if not l.lstrip().startswith(";;#") else l.strip() for l in _isa("gemm", extra).split("\n")]
+        lines = [l.split(";")[0].rstrip() if not l.lstrip().startswith(";;#") else l.strip() for l in _isa("gemm*", extra).split("\n")]
         inasm, checked, bad = False, 0, []
         code = []                                      # (text, in_asm) of real instructions, in order
         for l in lines:

@@ -160,31 +160,46 @@ def test_synth_is_deterministic_and_dyadic():
 
 
 def test_gemm_debug_build_compiles(tmp_path):
-    """the timing-ablation stamps / sentinels of gemm.hip exist only under -DDEVIAS_GEMM_DEBUG: that build must keep
-    compiling for gfx950, and the production object must not contain the s_memrealtime stamps"""
-    import shutil
+    """the timing-ablation stamps / sentinels of the GEMM units (build.GEMM_SOURCES and the gemm_*.h headers) exist only under -DDEVIAS_GEMM_DEBUG (VERDICT r1
+    item 7): that build of every unit must keep compiling for gfx950, and the production objects must not contain the s_memrealtime stamps"""
     import subprocess
+    from concurrent.futures import ThreadPoolExecutor
     from devias_amd import build as b
     if not os.path.exists(b.HIPCC):
         pytest.skip("hipcc not available")
-    src = os.path.join(b.CSRC, "gemm.hip")
-    out = tmp_path / "gemm_debug.s"
-    cmd = [b.HIPCC] + b.FLAGS + ["-DDEVIAS_GEMM_DEBUG", "-S", "--cuda-device-only", src, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    dbg = out.read_text()
+
+    def debug_isa(unit):
+        out = tmp_path / (unit + ".debug.s")
+        cmd = [b.HIPCC] + b._flags(unit) + ["-DDEVIAS_GEMM_DEBUG", "-S", "--cuda-device-only", os.path.join(b.CSRC, unit), "-o", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, (unit, r.stderr[-2000:])
+        return out.read_text()
+    with ThreadPoolExecutor(max_workers=min(len(b.GEMM_SOURCES), int(os.environ.get("MAX_JOBS", 16)), os.cpu_count() or 4)) as ex:
+        dbg = "\n".join(ex.map(debug_isa, b.GEMM_SOURCES))
     assert "s_memrealtime" in dbg
     # production build: every stamp sits inside an #ifdef DEVIAS_GEMM_DEBUG block of the source
-    depth, bad = 0, []
-    for ln, line in enumerate(open(src), 1):
-        t = line.strip()
-        if t.startswith("#ifdef DEVIAS_GEMM_DEBUG"):
-            depth += 1
-        elif t.startswith("#endif") and depth:
-            depth -= 1
-        elif re.search(r"\bst[0-3]\s*=\s*__builtin_amdgcn_s_memrealtime", line) and depth == 0 and not t.startswith("//"):     # (the stream-K hand-off timeout also reads the clock)
-            bad.append(ln)
-    assert not bad, bad
+    gemm_headers = [h for h in b.HEADERS if h.startswith("gemm")]
+    assert gemm_headers
+    for name in b.GEMM_SOURCES + gemm_headers:
+        depth, bad = 0, []
+        for ln, line in enumerate(open(os.path.join(b.CSRC, name)), 1):
+            t = line.strip()
+            if t.startswith("#ifdef DEVIAS_GEMM_DEBUG"):
+                depth += 1
+            elif t.startswith("#endif") and depth:
+                depth -= 1
+            elif re.search(r"\bst[0-3]\s*=\s*__builtin_amdgcn_s_memrealtime", line) and depth == 0 and not t.startswith("//"):     # (the stream-K hand-off timeout also reads the clock)
+                bad.append(ln)
+        assert not bad, (name, bad)
+
+
+def test_every_csrc_file_is_listed_in_the_build():
+    """a unit missing from build.SOURCES is never linked; a header missing from build.HEADERS means silently stale objects and a source_hash that does not change with the code"""
+    from devias_amd import build as b
+    on_disk = set(os.listdir(b.CSRC))
+    assert sorted(f for f in on_disk if f.endswith(".hip")) == sorted(b.SOURCES)
+    assert sorted(f for f in on_disk if f.endswith(".h")) == sorted(b.HEADERS)
+    assert len(set(b.SOURCES)) == len(b.SOURCES) and len(set(b.HEADERS)) == len(b.HEADERS)
 
 
 def test_published_column_sums_go_stale_safely_with_two_consumers():

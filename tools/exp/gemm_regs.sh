@@ -2,7 +2,7 @@
 # registers / scratch / in-loop full drains of every gemm256p instantiation: tools/exp/gemm_regs.sh [extra -D flags]
 cd "$(dirname "$0")/../.."
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=fast -Wno-unused-result -fno-gpu-rdc -mllvm -amdgpu-early-inline-all=true -mllvm -amdgpu-mfma-vgpr-form"
-/opt/rocm/bin/hipcc $FLAGS "$@" --cuda-device-only -S devias_amd/csrc/gemm.hip -o /tmp/gemm_regs.s || exit 1
+/opt/rocm/bin/hipcc $FLAGS "$@" --cuda-device-only -S devias_amd/csrc/gemm256p.hip -o /tmp/gemm_regs.s || exit 1      # (gemm256p_kernel's static-list instantiations; the dynamic-queue ones: gemm256.hip)
 python3 - <<'PY'
 import re
 L=open('/tmp/gemm_regs.s').read().split('\n')
