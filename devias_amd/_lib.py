@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 170                # devias_version() of the library these prototypes describe
+ABI_VERSION = 171                # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -52,12 +52,18 @@ class BlockArgs(Structure):          # devias_block_args
                [(n, c_void_p) for n in ("n1w", "n1b", "n2w", "n2b", "Wqkv", "Wp", "W1", "W2", "qkv_bias", "pb", "b1", "b2", "ds1", "ds2", "save", "ws")] + \
                [("ws_bytes", c_int64), ("sk_ws", c_void_p), ("sk_ws_bytes", c_int64)] + \
                [(n, c_void_p) for n in ("WqkvT", "WpT", "W1T", "W2T")] + \
-               [("WqkvS", c_void_p), ("qkv_biasS", c_void_p)]                     # ABI 166: optional transposed weight copies for the dgrad GEMMs; 167: the q-scaled copy of Wqkv / qkv_bias
+               [("WqkvS", c_void_p), ("qkv_biasS", c_void_p)] + \
+               [("defer_wgrad", c_int32)] + [(n, c_void_p) for n in ("keep_dhpre", "keep_dqkv", "keep_dx1", "keep_g2", "keep_g1")]
+    # ABI 166: optional transposed weight copies for the dgrad GEMMs; 167: the q-scaled copy of Wqkv / qkv_bias; 171: weight gradients left to the caller (devias_wgrad_group)
 
 
 class BlockGrads(Structure):         # devias_block_grads
     _fields_ = [(n, c_void_p) for n in ("dn1w", "dn1b", "dWqkv", "dbqkv", "dWp", "dbp", "dn2w", "dn2b", "dW1", "db1", "dW2", "db2", "dx_colsum")] + \
                [("db2_done", c_int32), ("dbq", c_void_p), ("dbv", c_void_p)]
+
+
+class WgradJob(Structure):           # devias_wgrad_job
+    _fields_ = [("dY", c_void_p), ("X", c_void_p), ("dW", c_void_p)] + [(n, c_int32) for n in ("M", "Nout", "Kin", "ldy", "ldx")] + [("beta", c_float)]
 
 
 class HeadArgs(Structure):           # devias_head_args
@@ -184,6 +190,10 @@ PROTOTYPES = {
     "devias_policy_gemm_cus": (c_int32, []),
     "devias_policy_small_m_split": (c_int32, [_I, _I, _I, _I]),
     "devias_policy_wgrad_split": (c_int32, [_I, _I, _I, _I]),
+    "devias_policy_wgrad_group_plan": (c_int32, [POINTER(c_int32), _I, _I, _I, POINTER(c_int32), _I, POINTER(c_int32), _I]),
+    "devias_wgrad_group_workspace_bytes": (c_int64, [POINTER(WgradJob), _I, _I]),
+    "devias_wgrad_group": (c_int, [POINTER(WgradJob), _I, _I, _P, _L, _P]),
+    "devias_encoder_block_wgrad_operands": (c_int, [POINTER(BlockArgs), _P, POINTER(BlockGrads), POINTER(WgradJob)]),
 }
 COUNTERS = {"gemm128_f32": 0, "gemm128_bf16": 1, "gemm_ss": 2, "gemm256": 3, "gemm256p": 4, "splitk_reduce": 5,
             "mhsa_fwd_bf16": 6, "mhsa_bwd_bf16": 7, "mhsa_fwd_f32": 8, "mhsa_bwd_f32": 9, "mhsa_bwd_fused": 10, "gemm_sk": 11, "gemm256w": 12, "gemm_smallm": 13, "gemm256d": 14,

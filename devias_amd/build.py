@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdevias_amd.so")
 # the GEMM: one unit per kernel family (two where one would compile for too long: gemm128.h, gemm256p.h) + the host side (gemm.hip); first in SOURCES, longest first, so that the longest compiles start first
-GEMM_SOURCES = ["gemm256.hip", "gemm256p.hip", "gemm128_bf16.hip", "gemm128_f32.hip", "gemm_ss.hip", "gemm256w.hip", "gemm_smallm.hip", "gemm.hip"]
+GEMM_SOURCES = ["gemm256.hip", "gemm256p.hip", "gemm128_bf16.hip", "gemm128_f32.hip", "gemm_ss.hip", "gemm256w.hip", "gemm_smallm.hip", "gemm_wgrad_group.hip", "gemm.hip"]
 SOURCES = GEMM_SOURCES + ["attn_bwd1w.hip", "slot_attn.hip", "layernorm.hip", "attention.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HEADERS = ["common.h", "roctx_shim.h", "attn1w.h", "gemm_common.h", "gemm_tile256.h", "gemm128.h", "gemm256p.h"]

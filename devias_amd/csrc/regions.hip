@@ -201,13 +201,21 @@ extern "C" int devias_encoder_block_bwd(const devias_block_args* a, const void* 
                                         void* scratch, int64_t scratch_bytes, void* stream) {
     RUN(block_check(a, "devias_encoder_block_bwd"));
     DEVIAS_REQUIRE(x && dx2 && dx && g && scratch && aligned16(scratch), "devias_encoder_block_bwd: null / unaligned argument");
-    DEVIAS_REQUIRE(g->dn1w && g->dn1b && g->dWqkv && (g->dbqkv || (g->dbq && g->dbv)) && g->dWp && g->dbp && g->dn2w && g->dn2b && g->dW1 && g->db1 && g->dW2 && g->dx_colsum &&
-                   (g->db2 || g->db2_done), "devias_encoder_block_bwd: null gradient destination");
+    // deferred weight gradients (ABI 171): the products of the mask are left to the caller, their operands dhpre / dqkv / dx1 go to the caller's buffers instead of the arena
+    const int defer = a->defer_wgrad & 15;
+    DEVIAS_REQUIRE(g->dn1w && g->dn1b && (g->dWqkv || (defer & 8)) && (g->dbqkv || (g->dbq && g->dbv)) && (g->dWp || (defer & 4)) && g->dbp && g->dn2w && g->dn2b &&
+                   (g->dW1 || (defer & 2)) && g->db1 && (g->dW2 || (defer & 1)) && g->dx_colsum && (g->db2 || g->db2_done), "devias_encoder_block_bwd: null gradient destination");
+    DEVIAS_REQUIRE(!defer || (a->keep_dhpre && a->keep_dqkv && a->keep_dx1 && aligned16(a->keep_dhpre) && aligned16(a->keep_dqkv) && aligned16(a->keep_dx1) &&
+                              (!a->ds2 || (a->keep_g2 && aligned16(a->keep_g2))) && (!a->ds1 || (a->keep_g1 && aligned16(a->keep_g1)))),
+                   "devias_encoder_block_bwd: defer_wgrad needs keep_dhpre / keep_dqkv / keep_dx1 (and keep_g2 / keep_g1 under ds2 / ds1), 16-byte aligned");
     const int B = a->B, N = a->N, D = a->D, H = a->H, hid = a->hidden, M = B * N;
     DEVIAS_REQUIRE(scratch_bytes >= devias_encoder_block_scratch_bytes(B, N, D, H, hid, a->dtype), "devias_encoder_block_bwd: scratch too small");
     const Ctx c{a->dtype, a->ws, a->ws_bytes, a->sk_ws, a->sk_ws_bytes, stream};
     const BlockSave s(a->save, B, N, D, H, hid, a->dtype);
-    const BlockScratch t(scratch, B, N, D, H, hid, a->dtype);
+    BlockScratch t(scratch, B, N, D, H, hid, a->dtype);
+    char *const dhpre = defer ? (char*)a->keep_dhpre : t.big, *const dqkv = defer ? (char*)a->keep_dqkv : t.big;
+    if (defer) t.dx1 = (char*)a->keep_dx1;
+    char *const tg2 = defer ? (char*)a->keep_g2 : t.g, *const tg1 = defer ? (char*)a->keep_g1 : t.g;      // the rescaled branch gradients (stochastic depth)
     devias_range r("encoder_block_bwd");
     // transposed weight copies for the dgrad GEMMs: bf16 only (the fp32 kernels stage through registers: no gain), option gemm_wt
     const bool wt = a->dtype == DEVIAS_BF16 && devias_options()[OPT_GEMM_WT] != 0;
@@ -220,27 +228,27 @@ extern "C" int devias_encoder_block_bwd(const devias_block_args* a, const void* 
     // ---- MLP branch (g2 = gradient of the branch output: dx2 scaled by the per-sample stochastic-depth factor, if any)
     const void* g2 = dx2;
     if (a->ds2) {
-        RUN(devias_row_scale_colsum(dx2, a->ds2, N, t.g, a->dtype, M, D, g->db2, 0.f, t.p_b2, (hipStream_t)stream));      // the rescaled copy and its column sums in one pass
-        g2 = t.g;
+        RUN(devias_row_scale_colsum(dx2, a->ds2, N, tg2, a->dtype, M, D, g->db2, 0.f, t.p_b2, (hipStream_t)stream));      // the rescaled copy and its column sums in one pass
+        g2 = tg2;
     } else if (!g->db2_done) {
         RUN(colsum(with_ws(t.p_b2), dx2, M, D, g->db2));                       // fc2 bias gradient (the caller had no ready-made column sums of dx2)
     }
-    RUN(wgrad(c, g2, s.hact, g->dW2, M, D, hid));
+    if (!(defer & 1)) RUN(wgrad(c, g2, s.hact, g->dW2, M, D, hid));
     // (the four dgrad GEMMs: on the caller's transposed weight copies where it keeps them -- both operands k-contiguous -- else the weight read k-strided; same bits)
     { Epi e; e.act = DEVIAS_ACT_DGELU; e.aux_in = s.hpre; e.colsum = g->db1;                                                                                   // (g2 W2) * gelu'(pre); db1 = colsum
-      if (W2T) RUN(gemm(with_ws(t.p_db1), g2, W2T, t.big, M, hid, D, D, D, 0, 0, e)); else RUN(gemm(with_ws(t.p_db1), g2, a->W2, t.big, M, hid, D, D, hid, 0, 1, e)); }
-    RUN(wgrad(c, t.big, s.u2, g->dW1, M, hid, D));
-    { Epi e; if (W1T) RUN(gemm(c, t.big, W1T, t.small, M, D, hid, hid, hid, 0, 0, e)); else RUN(gemm(c, t.big, a->W1, t.small, M, D, hid, hid, D, 0, 1, e)); }   // du2
+      if (W2T) RUN(gemm(with_ws(t.p_db1), g2, W2T, dhpre, M, hid, D, D, D, 0, 0, e)); else RUN(gemm(with_ws(t.p_db1), g2, a->W2, dhpre, M, hid, D, D, hid, 0, 1, e)); }
+    if (!(defer & 2)) RUN(wgrad(c, dhpre, s.u2, g->dW1, M, hid, D));
+    { Epi e; if (W1T) RUN(gemm(c, dhpre, W1T, t.small, M, D, hid, hid, hid, 0, 0, e)); else RUN(gemm(c, dhpre, a->W1, t.small, M, D, hid, hid, D, 0, 1, e)); }   // du2
     // + residual gradient; dbp = colsum(dx1) -- unless stochastic depth rescales dx1 first: then the column sum of the rescaled copy below is dbp (two deferred
     // jobs must not share a destination: they run side by side)
     RUN(ln_bwd(with_ws(t.p_ln2), t.small, s.x1, a->n2w, s.mean2, s.rstd2, dx2, t.dx1, g->dn2w, g->dn2b, 0.f, a->ds1 ? nullptr : g->dbp, M, D));
     // ---- attention branch
     const void* g1 = t.dx1;
     if (a->ds1) {
-        RUN(devias_row_scale_colsum(t.dx1, a->ds1, N, t.g, a->dtype, M, D, g->dbp, 0.f, t.p_bp, (hipStream_t)stream));
-        g1 = t.g;
+        RUN(devias_row_scale_colsum(t.dx1, a->ds1, N, tg1, a->dtype, M, D, g->dbp, 0.f, t.p_bp, (hipStream_t)stream));
+        g1 = tg1;
     }
-    RUN(wgrad(c, g1, s.o, g->dWp, M, D, D));
+    if (!(defer & 4)) RUN(wgrad(c, g1, s.o, g->dWp, M, D, D));
     // v_bias gradient: the column sum of d_o where the attention backward says so (softmax rows sum to one: sum_keys dV = sum_queries dO), from this GEMM's epilogue
     const bool dv_from_do = g->dbq && g->dbv && devias_mhsa_bwd_bias_dv_from_do(a->dtype, 1.0f);
     const int aflags = block_qpre(a) ? DEVIAS_ATTN_Q_PRESCALED : 0;      // (the arena's q third is q' = q * scale * log2 e: what forward decided from the same struct)
@@ -248,17 +256,29 @@ extern "C" int devias_encoder_block_bwd(const devias_block_args* a, const void* 
       const Ctx k = dv_from_do ? with_ws(t.p_v) : c;
       if (WpT) RUN(gemm(k, g1, WpT, t.small, M, D, D, D, D, 0, 0, e)); else RUN(gemm(k, g1, a->Wp, t.small, M, D, D, D, D, 0, 1, e)); }
     if (g->dbq && g->dbv)                                                   // dqkv + the q_bias / v_bias gradients (each to its own destination) from the same two kernels
-        RUN(devias_mhsa_bwd_bias_flags(s.qkv, s.o, t.small, s.lse, t.delta, t.big, B, N, H, 0.125f, a->dtype, 1.0f, 0, g->dbq, dv_from_do ? nullptr : g->dbv, t.p_q, t.p_v, aflags, stream));
+        RUN(devias_mhsa_bwd_bias_flags(s.qkv, s.o, t.small, s.lse, t.delta, dqkv, B, N, H, 0.125f, a->dtype, 1.0f, 0, g->dbq, dv_from_do ? nullptr : g->dbv, t.p_q, t.p_v, aflags, stream));
     else
-        RUN(devias_mhsa_bwd_flags(s.qkv, s.o, t.small, s.lse, t.delta, t.big, B, N, H, 0.125f, a->dtype, t.p_q, aflags, stream));                          // dqkv
-    RUN(wgrad(c, t.big, s.u, g->dWqkv, M, 3 * D, D));
+        RUN(devias_mhsa_bwd_flags(s.qkv, s.o, t.small, s.lse, t.delta, dqkv, B, N, H, 0.125f, a->dtype, t.p_q, aflags, stream));                          // dqkv
+    if (!(defer & 8)) RUN(wgrad(c, dqkv, s.u, g->dWqkv, M, 3 * D, D));
     if (g->dbq && g->dbv) {
     } else {
-        RUN(colsum(with_ws(t.p_q), t.big, M, 3 * D, g->dbqkv));
+        RUN(colsum(with_ws(t.p_q), dqkv, M, 3 * D, g->dbqkv));
     }
-    { Epi e; if (WqkvT) RUN(gemm(c, t.big, WqkvT, t.small, M, D, 3 * D, 3 * D, 3 * D, 0, 0, e)); else RUN(gemm(c, t.big, a->Wqkv, t.small, M, D, 3 * D, 3 * D, D, 0, 1, e)); }   // du
+    { Epi e; if (WqkvT) RUN(gemm(c, dqkv, WqkvT, t.small, M, D, 3 * D, 3 * D, 3 * D, 0, 0, e)); else RUN(gemm(c, dqkv, a->Wqkv, t.small, M, D, 3 * D, 3 * D, D, 0, 1, e)); }   // du
     RUN(ln_bwd(with_ws(t.p_ln1), t.small, x, a->n1w, s.mean1, s.rstd1, t.dx1, dx, g->dn1w, g->dn1b, 0.f, g->dx_colsum, M, D));
     RUN(devias_flush_deferred(&dl, (hipStream_t)stream));
+    return DEVIAS_OK;
+}
+
+extern "C" int devias_encoder_block_wgrad_operands(const devias_block_args* a, const void* dx2, const devias_block_grads* g, devias_wgrad_job jobs[4]) {
+    DEVIAS_REQUIRE(a && dx2 && g && jobs && a->save && a->keep_dhpre && a->keep_dqkv && a->keep_dx1 && (!a->ds2 || a->keep_g2) && (!a->ds1 || a->keep_g1),
+                   "devias_encoder_block_wgrad_operands: needs the save arena and the keep_* buffers");
+    const int D = a->D, hid = a->hidden, M = a->B * a->N;
+    const BlockSave s(a->save, a->B, a->N, D, a->H, hid, a->dtype);
+    jobs[0] = devias_wgrad_job{a->ds2 ? a->keep_g2 : dx2, s.hact, g->dW2, M, D, hid, D, hid, 0.f};
+    jobs[1] = devias_wgrad_job{a->keep_dhpre, s.u2, g->dW1, M, hid, D, hid, D, 0.f};
+    jobs[2] = devias_wgrad_job{a->ds1 ? a->keep_g1 : a->keep_dx1, s.o, g->dWp, M, D, D, D, D, 0.f};
+    jobs[3] = devias_wgrad_job{a->keep_dqkv, s.u, g->dWqkv, M, 3 * D, D, 3 * D, D, 0.f};
     return DEVIAS_OK;
 }
 

@@ -167,10 +167,22 @@ class EncoderBlockFn(Function):
         else:
             g2 = ops.row_scale(dx2, ds2, N)
             db2 = ops.colsum(g2, out=_gout(p_f2b))
-        dW2 = ops.wgrad(g2, hact, out=_gout(p_f2w))
+        # the weight gradients the queue takes (ops.wgrad_defer_mask; the same jobs in the same order as the fused region's): destination now, product at the flush
+        defer = ops.wgrad_defer_mask((p_f2w, p_f1w, p_pw, p_qkvw), cdt, x.shape[0], D, W1.shape[0], E1 is None and E2 is None)
+        jobs = []
+
+        def wgrad(i, dY, X, p_):
+            if not defer >> i & 1:
+                return ops.wgrad(dY, X, out=_gout(p_))
+            dW = _gout(p_)
+            if dW is None:
+                dW = torch.empty((dY.shape[1], X.shape[1]), dtype=torch.float32, device=dev)
+            jobs.append((ops.wgrad_job(dY, X, dW), dY, (X, dW.untyped_storage())))      # (the queue keeps dW's STORAGE: the object handed to autograd must stay unshared -- even a view of it would hold it --, see _gout)
+            return dW
+        dW2 = wgrad(0, g2, hact, p_f2w)
         db1 = dst(p_f1b, W1.shape[0])
         dhpre = ops.gemm(g2, W2, trans_b=True, act=ACT_DGELU, aux_in=hpre, colsum=db1)   # (g2 W2) * gelu'(pre); db1 = colsum
-        dW1 = ops.wgrad(dhpre, u2, out=_gout(p_f1w))
+        dW1 = wgrad(1, dhpre, u2, p_f1w)
         du2 = ops.gemm(dhpre, W1, trans_b=True)
         dbp = dst(p_pb, D)
         dx1, dn2w, dn2b = ops.layernorm_bwd(du2, x1, n2w_, mean2, rstd2, dres=dx2, dx_colsum=dbp,
@@ -184,7 +196,7 @@ class EncoderBlockFn(Function):
         else:
             g1 = ops.row_scale(dx1, ds1, N)
             dbp = ops.colsum(g1, out=dbp)
-        dWp = ops.wgrad(g1, o, out=_gout(p_pw))
+        dWp = wgrad(2, g1, o, p_pw)
         dbq, dbv = dst(p_qb, D), dst(p_vb, D)                                  # q_bias | (k: no bias) | v_bias, each to its own destination
         if ops.mhsa_bwd_dv_from_do(g1.dtype, adrop):
             # softmax rows sum to one: sum_keys dV = sum_queries dO -- the v_bias gradient is the column sum of d_o, taken from the GEMM that produces it
@@ -193,11 +205,13 @@ class EncoderBlockFn(Function):
         else:
             d_o = ops.gemm(g1, Wp, trans_b=True)
             dqkv = ops.mhsa_bwd(qkv, o, d_o, lse, B, N, H, scale, drop=adrop, bias_out=(dbq, dbv), q_prescaled=ctx.qpre)
-        dWqkv = ops.wgrad(dqkv, u, out=_gout(p_qkvw))
+        dWqkv = wgrad(3, dqkv, u, p_qkvw)
         du = ops.gemm(dqkv, Wqkv, trans_b=True)
         dxs = f32(D)
         dx, dn1w, dn1b = ops.layernorm_bwd(du, x, n1w_, mean1, rstd1, dres=dx1, dx_colsum=dxs, dgamma=_gout(p_n1w), dbeta=_gout(p_n1b))
         _publish_colsum(dx, dxs)
+        if jobs:
+            ops.wgrad_enqueue([j for j, _, _ in jobs], [(dY, X) for _, dY, X in jobs], dev)
         return (dx, dn1w, dn1b, dWqkv, dbq, dbv, dWp, dbp, dn2w, dn2b, dW1, db1, dW2, db2, None, None, None, None)
 
 

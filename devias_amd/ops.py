@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -190,6 +191,145 @@ def wgrad(dY: torch.Tensor, X: torch.Tensor, out: Optional[torch.Tensor] = None,
     K = X.shape[1]
     sk = auto_split_k(N, K, M, bk=64 if dY.dtype == torch.bfloat16 else 16)     # C is [N, K], the reduction runs over M
     return gemm(dY, X, trans_a=True, trans_b=True, out=out, out_f32=True, beta=beta, split_k=sk)
+
+
+# ---- grouped weight gradients (devias_wgrad_group) ------------------------------------------------------------------------------------------------
+# An encoder block's backward leaves its four weight-gradient products (dW2, dW1, dWp, dWqkv) to ONE queue; when WGRAD_GROUP blocks are pending -- and, for the
+# rest, in a callback the autograd engine runs before backward() returns -- the queue runs them as one grouped split-K launch + one combine.  The fused region and the
+# per-kernel Function enqueue the same jobs in the same order, so both paths keep the same bits.  The queue's references keep the operands alive (the block's
+# incoming gradient, its saved activations, dhpre / dqkv / dx1); the gradient tensors are returned to autograd at once and filled later on the same stream.
+# What this rests on: between a Function's return and the flush NOTHING reads the returned gradient tensor.  That holds when AccumulateGrad adopts it unread (the
+# parameter has no .grad, the tensor object is unshared -- the queue keeps storages, never tensors --, grad mode is off), and it is checked per weight by
+# wgrad_deferrable: no .grad, no tensor hooks, no post-accumulate hooks, no grad mode inside backward (create_graph), no anomaly mode (it scans every returned
+# gradient).  NOT checked, because Python cannot see them: a weight used twice in one graph (the engine sums its two gradients before AccumulateGrad -- the encoder
+# uses each weight once) and hooks registered on the AccumulateGrad NODE itself (torch's DistributedDataParallel does that; this project's GradSync uses
+# post-accumulate hooks, which are seen).  A host that needs either sets WGRAD_GROUP = 0.
+WGRAD_GROUP = int(os.environ.get("DEVIAS_WGRAD_GROUP", "4"))      # blocks per grouped launch (measured: profiles/wgrad_group.txt); 0 = every product at once, as before
+_WGRAD_MAX_JOBS = 64
+
+
+class _WgradQueue:
+    def __init__(self, stream):
+        self.stream, self.jobs, self.keep, self.blocks = stream, [], [], 0
+
+
+_wgrad_queues = {}       # (device index, stream handle) -> _WgradQueue
+_wgrad_ws = {}           # the grouped launch's partial tiles, grow-only per (device index, stream handle)
+_keep_free = {}          # (device index, bytes) -> retention buffers (dhpre | dqkv | dx1 of a region's backward) not lent out
+_keep_made = [0]
+
+
+def wgrad_job(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, beta: float = 0.0) -> "_lib.WgradJob":
+    _chk(dY, "wgrad_job.dY", torch.bfloat16); _chk(X, "wgrad_job.X", torch.bfloat16); _chk(dW, "wgrad_job.dW", torch.float32)
+    assert dY.shape[0] == X.shape[0] and dW.shape == (dY.shape[1], X.shape[1])
+    return _lib.WgradJob(dY.data_ptr(), X.data_ptr(), dW.data_ptr(), dY.shape[0], dY.shape[1], X.shape[1], dY.shape[1], X.shape[1], beta)
+
+
+def wgrad_group_plan(job_tiles, k_tiles: int, cus: int):
+    """devias_policy_wgrad_group_plan (no GPU needed): ([(tiles, split) per round], [(job, tile, first K-tile, K-tiles, partial index, round) per (round, workgroup)])"""
+    lib = _lib.load()
+    jt = (ctypes.c_int32 * len(job_tiles))(*job_tiles)
+    rounds = (ctypes.c_int32 * 128)()
+    n = lib.devias_policy_wgrad_group_plan(jt, len(job_tiles), k_tiles, cus, rounds, 64, None, 0)
+    if n < 0:
+        raise ValueError(lib.devias_last_error().decode())
+    units = (ctypes.c_int32 * (6 * n * cus))()
+    assert lib.devias_policy_wgrad_group_plan(jt, len(job_tiles), k_tiles, cus, rounds, 64, units, n * cus) == n
+    return [(rounds[2 * i], rounds[2 * i + 1]) for i in range(n)], [tuple(units[6 * i:6 * i + 6]) for i in range(n * cus)]
+
+
+def wgrad_group(jobs, cus: int = 0, device=None, stream: Optional[int] = None) -> None:
+    """devias_wgrad_group: dW_j = beta_j dW_j + dY_j^T X_j for every job (ops.wgrad_job) in one grouped launch; an ineligible list raises"""
+    lib = _lib.load()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    stream = _stream() if stream is None else stream
+    arr = (_lib.WgradJob * len(jobs))(*jobs)
+    nbytes = lib.devias_wgrad_group_workspace_bytes(arr, len(jobs), cus)
+    if nbytes < 0:
+        raise ValueError(lib.devias_last_error().decode())
+    key = (device.index or 0, stream)
+    ws = _wgrad_ws.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        _wgrad_ws.pop(key, None)
+        ws = _wgrad_ws[key] = torch.empty((max(nbytes // 4, 64),), dtype=torch.float32, device=device)
+    _lib.check(lib.devias_wgrad_group(arr, len(jobs), cus, ws.data_ptr(), ws.numel() * 4, stream), "devias_wgrad_group")
+
+
+def wgrad_deferrable(p: Optional[torch.Tensor]) -> bool:
+    """a weight's gradient may be filled after its Function has returned only if nothing can read it before the queue is flushed: no gradient yet (autograd then adopts
+    the returned tensor without reading it), no tensor hooks, no post-accumulate hooks (GradSync's)"""
+    return (WGRAD_GROUP > 0 and p is not None and p.grad is None and not getattr(p, "_backward_hooks", None) and not getattr(p, "_post_accumulate_grad_hooks", None)
+            and not torch.is_grad_enabled() and not torch.is_anomaly_enabled())
+
+
+def wgrad_defer_mask(params, dtype: torch.dtype, M: int, D: int, hid: int, plain: bool) -> int:
+    """bit i set = the i-th weight gradient of an encoder block (dW2, dW1, dWp, dWqkv) goes through the queue; 0 where the grouped kernel cannot serve the block's
+    shapes (it needs whole 256 x 256 tiles of bf16 and the option gemm256) or the caller says so (`plain` False: element dropout masks, which only the per-kernel path has)"""
+    if WGRAD_GROUP <= 0 and _keep_free:
+        _keep_made[0] -= sum(len(v) for v in _keep_free.values())
+        _keep_free.clear()                                 # switched off: give the retention buffers back
+    if not (WGRAD_GROUP > 0 and plain and dtype == torch.bfloat16 and D % 256 == 0 and hid % 256 == 0 and M % 64 == 0 and get_option("gemm256") != 0):
+        return 0
+    return sum(1 << i for i, p in enumerate(params) if wgrad_deferrable(p))
+
+
+def keep_buffer(nbytes: int, device) -> torch.Tensor:
+    """a retention buffer for one region backward's dhpre | dqkv | dx1: lent until the queue has launched the block's weight gradients (wgrad_flush gives it back)"""
+    free = _keep_free.setdefault((torch.device(device).index or 0, int(nbytes)), [])
+    if free:
+        return free.pop()
+    _keep_made[0] += 1
+    return torch.empty((int(nbytes),), dtype=torch.uint8, device=device)
+
+
+def wgrad_enqueue(jobs, keep, device, lent=None) -> None:
+    """called from a block's backward: `jobs` run at the next flush; `keep` is whatever must stay alive until then, `lent` a keep_buffer to give back"""
+    key = (torch.device(device).index or 0, _stream())
+    q = _wgrad_queues.get(key)
+    if q is None:
+        q = _wgrad_queues[key] = _WgradQueue(key[1])
+    if len(q.jobs) + len(jobs) > _WGRAD_MAX_JOBS:
+        _wgrad_flush_queue(key, q)
+    q.jobs += list(jobs)
+    q.keep.append((keep, lent))
+    q.blocks += 1
+    if q.blocks >= WGRAD_GROUP:
+        _wgrad_flush_queue(key, q)
+    else:
+        torch.autograd.Variable._execution_engine.queue_callback(wgrad_flush)       # runs before backward() returns; a no-op when nothing is pending
+
+
+def _wgrad_flush_queue(key, q) -> None:
+    jobs, keep = q.jobs, q.keep
+    q.jobs, q.keep, q.blocks = [], [], 0
+    if not jobs:
+        return
+    device = torch.device("cuda", key[0])
+    try:
+        wgrad_group(jobs, device=device, stream=q.stream)      # (wgrad_defer_mask admitted only jobs the grouped kernel takes: a refusal here is an error)
+    finally:
+        for _, lent in keep:
+            if lent is not None:
+                free = _keep_free.setdefault((key[0], lent.numel()), [])
+                if len(free) < WGRAD_GROUP:                # (the pool never holds more than a group's worth: a host that lowers WGRAD_GROUP gets the memory back)
+                    free.append(lent)
+                else:
+                    _keep_made[0] -= 1
+
+
+def wgrad_flush() -> None:
+    """launch everything that is pending (every stream's queue, each on its own stream)"""
+    for key, q in list(_wgrad_queues.items()):
+        _wgrad_flush_queue(key, q)
+
+
+def wgrad_pending() -> int:
+    return sum(len(q.jobs) for q in _wgrad_queues.values())
+
+
+def wgrad_keep_stats() -> Tuple[int, int]:
+    """(retention buffers alive, of those currently free)"""
+    return _keep_made[0], sum(len(v) for v in _keep_free.values())
 
 
 def cast(src: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:

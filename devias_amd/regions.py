@@ -135,8 +135,29 @@ class EncoderBlockRegionFn(Function):
         nscr = lib.devias_encoder_block_scratch_bytes(B, N, D, H, hid, a.dtype)
         scr = _scratch(nscr, dev)
         dx = torch.empty_like(x)
+        # the weight gradients the queue takes (ops.wgrad_defer_mask): the block skips them and writes dhpre | dqkv | dx1 to a retention buffer instead of its scratch
+        M = B * N
+        defer = ops.wgrad_defer_mask((p_f2w, p_f1w, p_pw, p_qkvw), cdt, M, D, hid, True)
+        kept = None
+        if defer:
+            es, al = x.element_size(), lambda n: (n + 255) // 256 * 256          # noqa: E731
+            nds = int(ds1 is not None) + int(ds2 is not None)          # stochastic depth: the rescaled branch gradients are operands too
+            kept = ops.keep_buffer(al(M * hid * es) + al(M * 3 * D * es) + (1 + nds) * al(M * D * es), dev)
+            a.defer_wgrad = defer
+            a.keep_dhpre = kept.data_ptr()
+            a.keep_dqkv = a.keep_dhpre + al(M * hid * es)
+            a.keep_dx1 = a.keep_dqkv + al(M * 3 * D * es)
+            nxt = a.keep_dx1 + al(M * D * es)
+            if ds2 is not None:
+                a.keep_g2, nxt = nxt, nxt + al(M * D * es)
+            if ds1 is not None:
+                a.keep_g1 = nxt
         _L.check(lib.devias_encoder_block_bwd(_ct.byref(a), x.data_ptr(), dx2.data_ptr(), dx.data_ptr(), _ct.byref(g), scr.data_ptr(), scr.numel(), ops._stream()),
                  "devias_encoder_block_bwd")
+        if defer:
+            jobs = (_L.WgradJob * 4)()
+            _L.check(lib.devias_encoder_block_wgrad_operands(_ct.byref(a), dx2.data_ptr(), _ct.byref(g), jobs), "devias_encoder_block_wgrad_operands")
+            ops.wgrad_enqueue([_L.WgradJob.from_buffer_copy(jobs[i]) for i in range(4) if defer >> i & 1], (dx2, save, [gd.out[i].untyped_storage() for i in (10, 8, 4, 2)]), dev, lent=kept)      # (storages, not tensors: the OBJECTS handed to autograd must stay unshared, see _gout)
         ctx.keep = ctx.args = None
         (dn1w, dn1b, dWqkv, dbq, dWp, dbp, dn2w, dn2b, dW1, db1, dW2, db2, dxs, dbv) = gd.out
         if ready is not None:

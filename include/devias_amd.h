@@ -47,6 +47,8 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     140 = (stream-K GEMM schedule, retired in 160; devias_gemm_args grew by sk_ws / sk_ws_bytes: recompile callers), devias_allreduce_bucket,
                                     150 = fused regions (devias_encoder_block_* / devias_agg_block_* / devias_head_*), devias_range_*,
                                     170 = devias_option_name, option slot_mfma (additive),
+                                    171 = devias_wgrad_group (+ devias_policy_wgrad_group_plan); devias_block_args grew by defer_wgrad / keep_dhpre / keep_dqkv / keep_dx1 / keep_g2 / keep_g1:
+                                          a caller compiled against ABI <= 170 must zero-extend the struct (recompile),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -246,6 +248,23 @@ typedef struct {
 int devias_gemm(const devias_gemm_args* args, void* stream);
 /* bytes of workspace devias_gemm needs for the given split_k (0 when split_k <= 1) */
 int64_t devias_gemm_workspace_bytes(int32_t M, int32_t N, int32_t split_k);
+
+/* Grouped weight gradients (ABI 171): dW_j[Nout_j, Kin_j] (fp32, contiguous) = beta_j dW_j + dY_j[M, Nout_j]^T X_j[M, Kin_j] for n_jobs products over the SAME M rows,
+ * as ONE split-K launch (one workgroup per CU walks a host-planned list of rounds of (tiles x split) units over the concatenated 256 x 256 tile list, the body of the
+ * 256 x 256 weight-gradient kernel) plus one combine launch for the split tiles.  Eligibility is that kernel's: bf16 operands, Nout % 256 == 0, Kin % 256 == 0,
+ * M % 64 == 0, 16-byte aligned bases, leading dimensions % 8 == 0, option gemm256 != 0; at most 64 jobs.  An ineligible list returns DEVIAS_EINVAL and launches nothing: the caller runs
+ * devias_gemm per product instead.  No atomics, no waiting between workgroups: results are bitwise reproducible, and a function of (jobs' shapes, M, workgroups) only.
+ * cus_override: 0 = devias_policy_gemm_cus() workgroups; > 0 = that many (a multiple of 8, at most the device's CUs; tests reach every schedule form at small shapes).
+ * ws: devias_wgrad_group_workspace_bytes() bytes, 16-byte aligned (may be NULL when that is 0).  Counts DEVIAS_CNT_GEMM256 once per job (+ DEVIAS_CNT_SPLITK_REDUCE once
+ * when a tile was split). */
+typedef struct {
+    const void* dY; const void* X;       /* bf16 [M, ldy], [M, ldx] */
+    float* dW;                           /* fp32 [Nout, Kin] */
+    int32_t M, Nout, Kin, ldy, ldx;
+    float beta;
+} devias_wgrad_job;
+int64_t devias_wgrad_group_workspace_bytes(const devias_wgrad_job* jobs, int32_t n_jobs, int32_t cus_override);      /* -1: ineligible list */
+int devias_wgrad_group(const devias_wgrad_job* jobs, int32_t n_jobs, int32_t cus_override, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Element-wise / data-movement helpers
@@ -561,6 +580,14 @@ typedef struct {
      * q' = q * scale * log2(e) rounded once, and the attention kernels of both directions run with DEVIAS_ATTN_Q_PRESCALED (see devias_mhsa_fwd_flags).  Backward reads
      * Wqkv / WqkvT (the unscaled copies) as before: dqkv holds the gradients with respect to the unscaled q, k, v.  The SAME struct must reach _fwd and _bwd of a block. */
     const void* WqkvS; const float* qkv_biasS;
+    /* ABI 171, backward only: defer_wgrad is a mask of the weight-gradient products the call does NOT run (bit 0 dW2, 1 dW1, 2 dWp, 3 dWqkv: the caller runs them later,
+     * e.g. several blocks' in one devias_wgrad_group launch; those destinations in devias_block_grads may be null).  Their operands must then outlive the call: with a
+     * non-zero mask dhpre [M, hidden], dqkv [M, 3D] and dx1 [M, D] (T) are written to the caller's keep_dhpre / keep_dqkv / keep_dx1 (all three required, 16-byte
+     * aligned) instead of the scratch arena -- no copies --, the other operands are dx2 and the save arena's hact, u2, o, u (devias_encoder_block_wgrad_operands).
+     * With stochastic depth the rescaled branch gradients are operands too: with ds2 (ds1) and a non-zero mask the rescaled copy of dx2 (dx1) is written to
+     * keep_g2 (keep_g1), [M, D] in T each, required then, instead of the scratch arena's shared piece. */
+    int32_t defer_wgrad;
+    void *keep_dhpre, *keep_dqkv, *keep_dx1, *keep_g2, *keep_g1;
 } devias_block_args;
 typedef struct {
     float *dn1w, *dn1b, *dWqkv, *dbqkv /* [3D]: dq_bias | (k: unused) | dv_bias */, *dWp, *dbp, *dn2w, *dn2b, *dW1, *db1, *dW2, *db2;
@@ -578,6 +605,9 @@ int devias_encoder_block_fwd(const devias_block_args* a, const void* x, void* x2
 /* x: the block's input again; dx2: gradient of its output; dx: gradient of its input */
 int devias_encoder_block_bwd(const devias_block_args* a, const void* x, const void* dx2, void* dx, const devias_block_grads* g,
                              void* scratch, int64_t scratch_bytes, void* stream);
+/* ABI 171: the four weight-gradient products of a block's backward as devias_wgrad_group jobs, in the order the block runs them (dW2, dW1, dWp, dWqkv): operands from
+ * dx2 (keep_g2 under ds2), the save arena and the keep_* buffers of `a`, destinations from `g` (null where not wanted: the job then has dW = NULL), beta 0 */
+int devias_encoder_block_wgrad_operands(const devias_block_args* a, const void* dx2, const devias_block_grads* g, devias_wgrad_job jobs[4]);
 
 /* Shared head + MaskPredictor (modeling_slot.py:392-393, 194-216): Z = slots Wh^T + bh [R,C]; Mk = sigmoid(W4 relu(W2 relu(W0 slots))) [R,G].
  * R = B*S rows, h1 / h2 = the MaskPredictor's hidden widths (512, 256). */
@@ -633,6 +663,13 @@ int devias_agg_block_bwd(const devias_agg_args* a, const void* x, const void* ds
 int32_t devias_policy_gemm_cus(void);      /* CUs the big-tile GEMM grids and the weight-gradient split-K sizing count on: device CUs - gemm_reserve_cus, multiple of 8 */
 int32_t devias_policy_small_m_split(int32_t M, int32_t N, int32_t K, int32_t trans_a);
 int32_t devias_policy_wgrad_split(int32_t Nout, int32_t Kin, int32_t Mrows, int32_t dtype);
+/* The plan of devias_wgrad_group (ABI 171; pure host arithmetic, no GPU): n_jobs products of job_tiles[j] tiles of 256 x 256, k_tiles = M / 64, `cus` workgroups (a multiple
+ * of 8).  Returns the number of rounds (-1: bad arguments or too little room).  rounds (optional): (tiles, split) per round, tiles * split <= cus, chosen by a dynamic
+ * programme that minimises sum(ceil(k_tiles / split) + 8); slabs of a round are per = ceil(k_tiles / split) K-tiles long (devias_gemm's rule).  units (optional): 6 int32 per
+ * (round, workgroup) slot -- job (-1: idle), tile of the job (row-major over its 256 x 256 tiles), first K-tile, K-tiles, partial tile index (-1: writes dW), round --;
+ * within a round the (slab, tile) pairs are laid out XCD-major: workgroup b takes pair (b % 8) * ceil(pairs / 8) + b / 8. */
+int32_t devias_policy_wgrad_group_plan(const int32_t* job_tiles, int32_t n_jobs, int32_t k_tiles, int32_t cus, int32_t* rounds, int32_t rounds_cap,
+                                       int32_t* units, int32_t units_cap);
 
 #ifdef __cplusplus
 }

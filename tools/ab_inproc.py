@@ -2,6 +2,8 @@
 """A/B of process-wide kernel options INSIDE one process: blocks of steps timed with HIP events, the option toggled between blocks in the order A B B A A B B A ...
 (no process restarts, no first-run / second-run bias: two separate bench.py runs differ by 0.1-0.3 ms whichever option they carry).
 usage: ab_inproc.py [bench.py flags] [hog=K] name=a,b [name=a,b ...]   e.g.  ab_inproc.py --model vit_large gemm_w4=0,1 gemm_tail_split=0,1
+name = wgrad_group flips the host's module constant devias_amd.ops.WGRAD_GROUP (blocks per grouped weight-gradient launch, 0 = the per-product launches) instead of a
+library option; a == b is an A/A comparison: the two halves of the blocks are kept apart, their difference is the spread a real delta has to beat.
 hog=K holds K compute units (128 KiB LDS each) on a side stream during every backward of every block that follows on the command line (hog=0 ends it),
 as bench.py --cu-hog does: the stand-in for a concurrent collective's kernels."""
 import os, sys, statistics as st
@@ -66,9 +68,13 @@ def main():
                 step()
             continue
         a, b = (int(v) for v in vals.split(","))
-        ts = {a: [], b: []}
-        for blk, v in enumerate([a, b, b, a] * 4):
-            ops.set_option(name, v)
+        ts = ([], [])
+        for blk, side in enumerate([0, 1, 1, 0] * 4):
+            v = (a, b)[side]
+            if name == "wgrad_group":
+                ops.WGRAD_GROUP = v
+            else:
+                ops.set_option(name, v)
             for _ in range(2):
                 step()
             torch.cuda.synchronize()
@@ -76,10 +82,14 @@ def main():
             for _ in range(10):
                 step()
             e1.record(); torch.cuda.synchronize()
-            ts[v].append(e0.elapsed_time(e1) / 10)
-        ops.set_option(name, b)
-        print(f"{name}: {a} -> median {st.median(ts[a]):.3f} ms (min {min(ts[a]):.3f}, max {max(ts[a]):.3f});  {b} -> median {st.median(ts[b]):.3f} ms (min {min(ts[b]):.3f}, max {max(ts[b]):.3f});"
-              f"  delta {st.median(ts[b]) - st.median(ts[a]):+.3f} ms", flush=True)
+            ts[side].append(e0.elapsed_time(e1) / 10)
+        if name == "wgrad_group":                      # (the A B B A order ends on A: leave b in force for the comparisons that follow, as always)
+            ops.WGRAD_GROUP = b
+        else:
+            ops.set_option(name, b)
+        ta, tb = ts
+        print(f"{name}: {a} -> median {st.median(ta):.3f} ms (min {min(ta):.3f}, max {max(ta):.3f});  {b} -> median {st.median(tb):.3f} ms (min {min(tb):.3f}, max {max(tb):.3f});"
+              f"  delta {st.median(tb) - st.median(ta):+.3f} ms", flush=True)
 
 
 main()
