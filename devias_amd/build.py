@@ -18,18 +18,20 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdevias_amd.so")
 # the GEMM: one unit per kernel family (two where one would compile for too long: gemm128.h, gemm256p.h) + the host side (gemm.hip); first in SOURCES, longest first, so that the longest compiles start first
 GEMM_SOURCES = ["gemm256.hip", "gemm256p.hip", "gemm128_bf16.hip", "gemm128_f32.hip", "gemm_ss.hip", "gemm256w.hip", "gemm_smallm.hip", "gemm_wgrad_group.hip", "gemm.hip"]
-SOURCES = GEMM_SOURCES + ["attn_bwd1w.hip", "slot_attn.hip", "layernorm.hip", "attention.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "probe.hip"]
+# the attention: its kernel units (attn_common.h says which kernels share one, and why) + the host side (attention.hip)
+ATTN_SOURCES = ["attn_bwd1w.hip", "attn_mfma16.hip", "attn_fwd.hip", "attn_f32.hip", "attention.hip"]
+SOURCES = GEMM_SOURCES + ATTN_SOURCES + ["slot_attn.hip", "layernorm.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-HEADERS = ["common.h", "roctx_shim.h", "attn1w.h", "gemm_common.h", "gemm_tile256.h", "gemm128.h", "gemm256p.h"]
+HEADERS = ["common.h", "roctx_shim.h", "attn_common.h", "attn1w.h", "gemm_common.h", "gemm_tile256.h", "gemm128.h", "gemm256p.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wno-unused-result",
          "-fno-gpu-rdc", "-mllvm", "-amdgpu-early-inline-all=true",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]   # keep MFMA accumulators in VGPRs: no v_accvgpr_* shuffles around the VALU epilogues
 
 
-# per-file additions.  attention.hip: no SLP vectorisation -- the compiler packs adjacent scalar fp32 adds / multiplies of the softmax arithmetic into v_pk_* instructions,
+# per-file additions.  Every attention unit: no SLP vectorisation -- the compiler packs adjacent scalar fp32 adds / multiplies of the softmax arithmetic into v_pk_* instructions,
 # and a packed fp32 instruction beside MFMAs costs more issue time than the two it replaces (MI355X_MICROARCH.md, per-instruction constants): forward attention -4 %
 # (profiles/r4_packed_fp32.txt)
-FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "attn_bwd1w.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {src: ["-fno-slp-vectorize"] for src in ATTN_SOURCES}
 
 
 def _flags(src: str):

@@ -2,15 +2,13 @@
 // MFMAs on literal accumulator registers, AGPR helpers.  Both kernels stream 32-row slices of two [rows][64] bf16 operands (Q | dO, resp. K | V) through an LDS ring
 // and keep their per-wave operands and accumulators in AGPRs named literally in inline asm (the compiler must touch no AGPR itself: tests/test_build_cpu.py).
 #pragma once
-#include "common.h"
+#include "attn_common.h"      // (LOG2E, LN2, f32x16, lds_void_ptr, fast_exp2, cvt_pk_bf16)
 #include <utility>
+
+using namespace attn_units;
 
 namespace {
 
-constexpr float LOG2E_1W = 1.4426950408889634f;
-constexpr float LN2_1W = 0.6931471805599453f;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef __attribute__((address_space(3))) const char* lds_cptr;
 
 enum { IMG_BYTES = 4096, STAGE_BYTES = 2 * IMG_BYTES };
@@ -22,12 +20,6 @@ enum { IMG_BYTES = 4096, STAGE_BYTES = 2 * IMG_BYTES };
 // must take disjoint chunk sets -> bit 2 of swz = (row >> 1) & 1.  Both kinds of read are conflict-free (measured: SQ_LDS_BANK_CONFLICT = 0).
 __device__ __forceinline__ int swz(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
 __device__ __forceinline__ int img_off(int row, int c) { return row * 128 + ((c ^ swz(row)) << 4); }
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
-    const bf16x2 t = {(bf16)a, (bf16)b};
-    return *reinterpret_cast<const unsigned*>(&t);
-}
 
 // ---- MFMAs on literal accumulator registers: the compiler sees neither the AGPRs nor the instruction (no hazard recognizer, no register allocation for them) ----
 // D (VGPRs) = A (VGPRs) x B (AGPRs a[BREG .. BREG + 3]) + C (VGPRs): the first k-step of a score / dP tile, started from the row constants

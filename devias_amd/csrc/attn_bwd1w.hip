@@ -1,6 +1,6 @@
 // Attention backward, dK / dV kernel in its one-wave-per-SIMD form (bf16, head dim 64, non-causal; model/modeling_slot.py:105-112 backward).
 //
-// Why: the two-waves-per-SIMD kernel (attention.hip: mhsa_bwd_dkdv_bf16_kernel) ran 13-44 % ABOVE the back-to-back sum of its own MFMA and VALU
+// Why: the two-waves-per-SIMD kernel (attn_mfma16.hip: mhsa_bwd_dkdv_bf16_kernel) ran 13-44 % ABOVE the back-to-back sum of its own MFMA and VALU
 // issue -- 44 % of its wave cycles parked on waits -- because nothing in a wave overlaps its matrix phase with its softmax phase and two phase-locked waves per
 // SIMD do not either.  Here ONE wave owns a SIMD and the whole 512-register file, and the overlap is built into its instruction stream:
 //
@@ -41,7 +41,6 @@
 
 namespace {
 
-constexpr float LOG2E = LOG2E_1W;
 enum { NSTATG = 4 /* statistics ring: groups of four slices, 1 KiB each */ };
 
 // AGPR map (asm-owned: claimed once, never touched by the compiler -- audited in tests/test_build_cpu.py):
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(NW * QS * 64) void mhsa_bwd_dkdv1w_kernel(const bf1
     const int nsl_all = Npad >> 5;                      // query slices
     const int nsl = QS > 1 ? (nsl_all - wq + QS - 1) / QS : nsl_all;      // ... of this wave
     const int ngrp = (nsl_all + 3) >> 2;                // statistics pieces (groups of four slices) per head
-    // item -> (batch, head, key block).  xcd & 1: all workgroups of one (batch, head) on one XCD (attention.hip head_map): its Q / dO rows stay in that L2.
+    // item -> (batch, head, key block).  xcd & 1: all workgroups of one (batch, head) on one XCD (attn_common.h head_map): its Q / dO rows stay in that L2.
     // PERSIST (whole 256-key blocks, xcd order only): the grid is a multiple of 8 workgroups, workgroup w takes items w, w + grid, ... -- an item stays on the
     // XCD of its head, and a head's blocks run at the same time on neighbouring workgroups
     const int nitems = PERSIST ? nblk * H * B : 0, istride = PERSIST ? (int)gridDim.x : 0;
@@ -249,7 +248,7 @@ __global__ __launch_bounds__(NW * QS * 64) void mhsa_bwd_dkdv1w_kernel(const bf1
     // ---- K / V fragments -> AGPRs (B operands: lane = key r32 of key block kb, d = 16 ks + 8 hi .. + 8); accumulators = 0 ------------------------------------------
     agpr_claim();
     auto fill_kv = [&]() {
-        const float ksc = (xcd & 2) ? 1.0f : scale * LOG2E;      // (xcd bit 1 = ATTN_QPRE, attention.hip: q already holds q * scale * log2 e -- the scores are then the forward's own products)
+        const float ksc = (xcd & 2) ? 1.0f : scale * LOG2E;      // (xcd bit 1 = ATTN_QPRE, attn_common.h: q already holds q * scale * log2 e -- the scores are then the forward's own products)
         sfor<8>([&](auto I) {
             constexpr int f = decltype(I)::value;
             sfor<4>([&](auto J) {
@@ -538,7 +537,7 @@ __global__ __launch_bounds__(NW * QS * 64) void mhsa_bwd_dkdv1w_kernel(const bf1
                         sk[e] += *reinterpret_cast<const f32x4*>(smem_all + w * 32768 + off);
                         sv[e] += *reinterpret_cast<const f32x4*>(smem_all + w * 32768 + off + 256);
                     }
-                    sk[e] *= (xcd & 2) ? LN2_1W : scale;
+                    sk[e] *= (xcd & 2) ? LN2 : scale;
                 }
                 if (key < N) {
                     bf16* dst = dqkv + ((int64_t)b * N + key) * RS + h * 64 + 8 * c8;
@@ -559,7 +558,7 @@ __global__ __launch_bounds__(NW * QS * 64) void mhsa_bwd_dkdv1w_kernel(const bf1
         // 128-byte half), then stores of eight whole rows per instruction.  Lane (hi, key r32 of block kb) holds d = 32 db + 8 jj + 4 hi .. + 4 of its key's rows ------
         if constexpr (!(DKDV_ABL & 2048)) {
             char* tile = smem + EPI_OFF + wave * 16384;
-            const float dksc = (xcd & 2) ? LN2_1W : scale;      // dK = scale dS^T q = ln 2 dS^T q'
+            const float dksc = (xcd & 2) ? LN2 : scale;      // dK = scale dS^T q = ln 2 dS^T q'
             sfor<16>([&](auto I) {
                 constexpr int db = (decltype(I)::value >> 3) & 1, kb = (decltype(I)::value >> 2) & 1, jj = decltype(I)::value & 3;
                 constexpr int ra = (db * 2 + kb) * 16 + 4 * jj;
@@ -614,7 +613,7 @@ extern "C" int devias_debug_dkdv_stamps(uint64_t* out, int32_t n) {
 #endif
 }
 
-// launched by attention.hip (mhsa_bwd_impl) behind the dQ kernel, which has written `stat`: the whole 256-key blocks of every head, then the ragged rest.
+// launched by attention.hip (mhsa_bwd) behind the dQ kernel, which has written `stat`: the whole 256-key blocks of every head, then the ragged rest.
 // persistent != 0 (and the XCD order, and tensors below 2 GiB so that an item is a 32-bit buffer offset): one workgroup per CU walks the 256-key blocks
 int devias_attn_dkdv1w_launch(const void* qkv, const void* d_o, const float* stat, void* dqkv, int B, int N, int Npad, int H, float scale, int xcd_flag, int persistent,
                               hipStream_t st) {

@@ -141,7 +141,7 @@ def _mix32(x: np.ndarray) -> np.ndarray:
 
 
 def attn_drop_mask(keep: float, seed: int, B: int, H: int, N: int) -> torch.Tensor:
-    """The mask devias_mhsa_fwd_dropout / _bwd_dropout apply to the softmax matrix (include/devias_amd.h, csrc/attention.hip drop_rowkey / drop_scale),
+    """The mask devias_mhsa_fwd_dropout / _bwd_dropout apply to the softmax matrix (include/devias_amd.h, csrc/attn_common.h drop_rowkey / drop_scale),
     restated in numpy: [B, H, N, N] fp32 of 0 or 1 / keep.  It stands in for nn.Dropout(attn_drop)'s mask (model/modeling_slot.py:90,110), which the
     reference draws from torch's generator: tests/golden/make_goldens.py hands THIS mask to the reference's F.dropout call."""
     M = np.uint64(0xFFFFFFFF)

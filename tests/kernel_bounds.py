@@ -12,8 +12,8 @@ inputs are graded so that every tile, third, wave slice and ragged tail holds ev
 Unit roundoffs: u_bf16 = 2^-8, u_fp32 = 2^-24.   excess(out, ref, bound) = max |out - ref| / bound;   a test asserts excess <= 1.
 
 Each *_ref function returns (ref, bound) tensors of the output's shape (or a dict of such pairs).  One named term per rounding the
-kernel's design makes, nothing else:  (Kernel sources are cited by file name: gemm.hip, gemm_common.h, common.h, layernorm.hip, attention.hip, attn_bwd1w.hip
-live in devias_amd/csrc/, devias_amd.h is include/devias_amd.h.)
+kernel's design makes, nothing else:  (Kernel sources are cited by file name: gemm.hip, gemm_common.h, common.h, layernorm.hip, attn_fwd.hip, attn_mfma16.hip, attn_f32.hip,
+attn_bwd1w.hip live in devias_amd/csrc/, devias_amd.h is include/devias_amd.h.)
 
 GEMM (devias_gemm, every layout and kernel form; include/devias_amd.h "epilogue order")
     pre   = A B + bias                      fp32 accumulation, any order:     e_pre = (K + 8) u_fp32 (|A||B| + |bias|)
@@ -41,9 +41,9 @@ LayerNorm (devias_amd/csrc/layernorm.hip: one wave per row, fp32 statistics, two
               dres is added in fp32 BEFORE the one rounding of dx (layernorm.hip:205-211); dx_colsum sums the fp32 values before rounding (:207).
               The reference takes the same saved mean / rstd tensors the kernel is given.
 
-MHSA forward (devias_amd/csrc/attention.hip; bf16: q' = bf16(q c), c = scale log2 e, attention.hip:402-415; P rounded to bf16 for the P V product; o rounded once)
+MHSA forward (devias_amd/csrc/attn_fwd.hip; bf16: q' = bf16(q c), c = scale log2 e, attn_fwd.hip:49-59; P rounded to bf16 for the P V product; o rounded once)
     o:   u (|o| + sum_j p_j |v_j| + sum_j p_j T_j |v_j - o|) + 64 u_fp32 (sum_j p_j |v_j| + sum_j p_j T_j |v_j - o|),   T_j = scale sum_d |q_d| |k_jd|
-         The last term is the fp32 accumulation of a score's 64 products (fp32 kernel: the sequential FMA chain of attention.hip:1006-1008; bf16: the MFMAs' fp32
+         The last term is the fp32 accumulation of a score's 64 products (fp32 kernel: the sequential FMA chain of attn_f32.hip:45-47; bf16: the MFMAs' fp32
          accumulators).  It is invisible next to u_bf16, but with u = u_fp32 the q-rounding term alone counts ONE rounding per score where the kernel makes 64:
          without it, at this slack, the fp32 forward kernel measured 1.18 at B, N, H = 1, 1569, 1, logit std 6 (0.44 with it).
     lse: u sum_j p_j T_j  (+ the fp32 floor 64 u_fp32 (sum_j p_j T_j + 1) + 4 u_fp32 |lse|)
@@ -52,13 +52,13 @@ MHSA forward (devias_amd/csrc/attention.hip; bf16: q' = bf16(q c), c = scale log
 
 MHSA backward (include/devias_amd.h:256-277; dS = P o (dP - delta), delta = rowsum(dO o O) from the STORED o)
     kernel probabilities  p^ = p (1 + eps),  |eps_ij| <= E_ij:
-        plain path      E_ij = u (T_ij + sum_j p_j T_j): the backward rounds q c (dQ kernel, attention.hip:649) or k c (one-wave dK / dV kernel,
-                        attn_bwd1w.hip:252) or nothing (two-wave kernel, attention.hip:912) while the saved lse came from the forward's q c
+        plain path      E_ij = u (T_ij + sum_j p_j T_j): the backward rounds q c (dQ kernel, attn_mfma16.hip:204-208) or k c (one-wave dK / dV kernel,
+                        attn_bwd1w.hip:251-256) or nothing (two-wave kernel, attn_mfma16.hip:471) while the saved lse came from the forward's q c
                         (devias_amd.h:273-274: "differ ... by two bf16 roundings")
         pre-scaled path E_ij = 0: all kernels multiply the SAME bf16 operands (devias_amd.h:274-275)
         both            + 64 u_fp32 (T_ij + sum_j p_j T_j + 1)
     delta:  sum_d |dO_d| bound_o_d + 64 u_fp32 sum_d |dO_d o_d|             (o is an input that carries the forward's bound)
-    dS:     p ((E + u) |dP - delta| + 64 u_fp32 |dO||v| + e_delta)          (P and dS are rounded to bf16 for their MFMAs: attention.hip:925-929)
+    dS:     p ((E + u) |dP - delta| + 64 u_fp32 |dO||v| + e_delta)          (P and dS are rounded to bf16 for their MFMAs: attn_mfma16.hip:323, 484-489)
     dQ = scale dS k,  dK = scale dS^T q,  dV = P^T dO:  the propagated term + u_out |result| + 64 u_fp32 of the absolute products
     dbq / dbv (the _bias entry point): fp32 column sums over all B N rows (from the accumulators in bf16; dbv = colsum(dO) where
     devias_mhsa_bwd_bias_dv_from_do says so -- the same value, softmax rows sum to one).

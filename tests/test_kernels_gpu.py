@@ -957,6 +957,46 @@ def test_mhsa_q_prescaled_scores_are_the_forwards(B, N, H, amp, attn_options):
                                                                                  for k, e in err.items()))
 
 
+_ATTN_CFG_CASE = {}
+
+
+def _attn_cfg_case(B, N, H, scale):
+    """inputs and float64 references of test_mhsa_every_attn_cfg_shape, computed once: they do not depend on the option"""
+    import kernel_bounds as kb
+    if not _ATTN_CFG_CASE:
+        for std, koff in kb.ATTN_GENERATORS:
+            qkv, d_o = kb.attention_inputs(B, N, H, torch.bfloat16, logit_std=std, seed=1000, device=DEV, key_offset=koff)
+            _ATTN_CFG_CASE[std, koff] = (qkv, d_o, kb.mhsa_fwd_ref(qkv, B, N, H, scale, torch.bfloat16, q_rounded=True),
+                                         kb.mhsa_bwd_ref(qkv, d_o, B, N, H, scale, torch.bfloat16, plain=True))
+    return _ATTN_CFG_CASE
+
+
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 6, 7])
+def test_mhsa_every_attn_cfg_shape(cfg, attn_options):
+    """Every kernel shape option attn_cfg selects, launched on its own: forward 6 = the 16x16x32 kernel (128 queries per workgroup), 7 = the 32x32x16 kernel on two
+    waves (64), otherwise on four (128); dQ 1 = <4, 2> (128 queries per workgroup, 128 threads), 2 = <4, 4> (256, 256), 3 = <2, 2> (64, 128), otherwise <2, 4> (128, 256).
+    N = 321 is ragged against every one of those divisors and gives the one-wave dK / dV kernel one whole 256-key block plus a rest launch; B H = 8 keeps the XCD-aware
+    linear grid.  A wrong grid or block size leaves rows unwritten or written twice: each element is held to the float64 bounds of tests/kernel_bounds.py, as in
+    tests/test_kernel_bounds_gpu.py::test_mhsa (same generators, same slack)."""
+    import kernel_bounds as kb
+    o = attn_options
+    B, H, N, scale = 2, 4, 321, 0.125
+    o.set_option("attn_cfg", cfg)
+    where = lambda i: kb.where_attn(i, N, H)  # noqa: E731
+    for (std, koff), (qkv, d_o, rf, rb) in _attn_cfg_case(B, N, H, scale).items():
+        o.counters(reset=True)
+        out, lse = o.mhsa_fwd(qkv, B, N, H, scale)
+        dqkv = o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, scale)
+        torch.cuda.synchronize()
+        cnt = o.counters()
+        assert cnt["mhsa_fwd_bf16"] == 1 and cnt["mhsa_bwd_bf16"] == 1 and cnt["dkdv1w"] == 1 and cnt["dkdv1w_rest"] == 1, cnt
+        ratios = {"out": kb.check(f"mhsa_fwd out (attn_cfg {cfg})", out, *rf["out"], where), "lse": kb.check(f"mhsa_fwd lse (attn_cfg {cfg})", lse, *rf["lse"])}
+        g = dqkv.reshape(B * N, 3, H * 64)
+        for i, name in enumerate(("dq", "dk", "dv")):
+            ratios[name] = kb.check(f"mhsa_bwd {name} (attn_cfg {cfg})", g[:, i].contiguous(), *rb[name], where)
+        print(f"[bound] mhsa attn_cfg={cfg} {(B, N, H)} std={std} koff={koff} worst ratio " + " ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+
+
 # ------------------------------------------------------------------------------------------------ folded slot attention
 def _slotf_ref(qp, c, B, S, N, h, D, scale):
     q = qp.reshape(B, S, h, D).permute(0, 2, 1, 3)                    # [B,h,S,D]

@@ -38,7 +38,7 @@ def test_oracle_matches_reference_golden_with_dropout():
 
 def test_attn_drop_mask_statistics_and_known_values():
     """the kernels' attention-mask hash, restated in numpy: keep fraction, independence across seeds / heads, and pinned values (a change of the hash
-    in csrc/attention.hip without the oracle -- or the reverse -- fails the GPU tests; a change of both fails here)"""
+    in csrc/attn_common.h without the oracle -- or the reverse -- fails the GPU tests; a change of both fails here)"""
     m = ref_cpu.attn_drop_mask(0.9, 0x0123456789ABCDEF, 2, 3, 128)
     assert m.shape == (2, 3, 128, 128) and abs(float((m > 0).float().mean()) - 0.9) < 0.01
     assert float(m.max()) == float(np.float32(1) / np.float32(0.9))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the compiled device code of two source trees kernel by kernel: for moves of kernels between translation units, which must not change them.
 
-    python tools/kernel_isa_diff.py TREE_A TREE_B [--units-a gemm.hip] [--units-b gemm128.hip gemm256.hip ...] [--keep DIR] [--jobs N]
+    python tools/kernel_isa_diff.py TREE_A TREE_B [--units-a gemm.hip] [--units-b gemm128.hip gemm256.hip ...] [--map OLD_KEY=NEW_KEY ...] [--keep DIR] [--jobs N]
 
 Every unit of a tree is compiled with that tree's own `devias_amd.build._flags(unit) --cuda-device-only -S`, once as released and once with
 -DDEVIAS_GEMM_DEBUG (units default to the tree's build.GEMM_SOURCES, or gemm.hip where a tree has no such list).  Kernels are keyed by their
@@ -10,6 +10,8 @@ Per kernel it prints a verdict -- identical / differs (lines, and where: prologu
 and requires equal descriptors (.amdhsa_* values: VGPR / AGPR / SGPR counts, LDS bytes, scratch) and equal MFMA counts.  Before the diff it drops comments and
 .loc / .file / .ident lines and replaces what differs by construction: __hip_cuid_<hash>, mangled names, and the per-unit counters in local labels
 (.LBB<n>_, .Lpost_getpc<n>, .Lfunc_end<n>, .Ltmp<n>).  It only normalises and diffs.  Exit status 1 if a kernel is missing or added, or a descriptor or MFMA count differs.
+--map OLD_KEY=NEW_KEY (repeatable): a kernel of tree A whose key changed in tree B (a template parameter added or dropped) is compared with that successor
+instead of being reported LOST / ADDED.
 --keep DIR keeps the assembly there (DIR/a, DIR/b) and reuses files already present."""
 import argparse
 import difflib
@@ -109,6 +111,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("tree_a"); ap.add_argument("tree_b")
     ap.add_argument("--units-a", nargs="+"); ap.add_argument("--units-b", nargs="+")
+    ap.add_argument("--map", action="append", default=[], metavar="OLD_KEY=NEW_KEY")
     ap.add_argument("--keep"); ap.add_argument("--jobs", type=int, default=min(int(os.environ.get("MAX_JOBS", 16)), os.cpu_count() or 4))
     args = ap.parse_args()
     tmp = None if args.keep else tempfile.TemporaryDirectory()
@@ -127,6 +130,8 @@ def main():
         ka, kb = {}, {}
         for t in texts[:na]:
             ka.update(kernels_of(t))
+        for old, new in (m.split("=", 1) for m in args.map):
+            ka[new] = ka.pop(old)          # (a key that tree A does not have is an error)
         for t in texts[na:]:
             kb.update(kernels_of(t))
         print(f"==== {'-DDEVIAS_GEMM_DEBUG' if debug else 'release'}: {len(ka)} kernels in A, {len(kb)} in B")
