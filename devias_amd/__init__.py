@@ -4,7 +4,7 @@ Importing the package is cheap and GPU-free; the HIP library is loaded on first 
 error (there is no CPU or eager-PyTorch fallback for the hot path)."""
 __version__ = "0.1.0"
 
-__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch"]
+__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma"]
 
 
 def __getattr__(name):
@@ -18,4 +18,7 @@ def __getattr__(name):
     if name == "train_class_batch":
         from .engine_for_slot import train_class_batch
         return train_class_batch
+    if name == "ModelEma":
+        from .ema import ModelEma
+        return ModelEma
     raise AttributeError(name)

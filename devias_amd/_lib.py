@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 171                # devias_version() of the library these prototypes describe
+ABI_VERSION = 172                # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -165,6 +165,8 @@ PROTOTYPES = {
     "devias_grad_sumsq_multi": (c_int, [_P, _P, _P, _I, _P, _P]),
     "devias_clip_coef": (c_int, [_P, _I, _F, _P, _P]),
     "devias_adamw_multi": (c_int, [_P, _P, _P, _I, _F, _F, _F, _F, _P, _P]),
+    "devias_adamw_ema_multi": (c_int, [_P, _P, _P, _I, _F, _F, _F, _F, _P, _F, _F, _P]),
+    "devias_ema_multi": (c_int, [_P, _P, _P, _I, _F, _F, _P]),
     "devias_fame_diff_color": (c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "devias_fame_blur": (c_int, [_P, _P, _I, _I, _I, _I, _F, _P]),
     "devias_fame_seg_refine": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P]),

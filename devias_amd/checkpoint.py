@@ -113,14 +113,18 @@ def find_latest_checkpoint(output_dir: str) -> Optional[str]:
     return os.path.join(output_dir, "checkpoint-%d.pth" % latest) if latest >= 0 else None
 
 
-def auto_resume(output_dir: str, model: torch.nn.Module, optimizer=None, scaler=None) -> int:
-    """utils/utils.py:467-500: returns the epoch to start from (0 when nothing to resume)."""
+def auto_resume(output_dir: str, model: torch.nn.Module, optimizer=None, scaler=None, model_ema=None) -> int:
+    """utils/utils.py:467-500: returns the epoch to start from (0 when nothing to resume).  With a `model_ema` (devias_amd.ema.ModelEma) the checkpoint's
+    'model_ema' entry is loaded into the shadow.  The reference's own resume (:494-495) hands that entry to timm's _load_checkpoint, which looks for a
+    'state_dict_ema' key inside it, finds none and silently keeps the freshly initialised shadow; here the shadow is restored."""
     path = find_latest_checkpoint(output_dir)
     if path is None:
         return 0
     ck = torch.load(path, map_location="cpu", weights_only=False)
     model.load_state_dict(ck["model"])
     print("Resume checkpoint %s" % path)
+    if model_ema is not None and "model_ema" in ck:
+        model_ema.load_state_dict(ck["model_ema"])
     start = 0
     if "optimizer" in ck and "epoch" in ck:
         if optimizer is not None:

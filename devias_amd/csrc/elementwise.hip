@@ -249,9 +249,23 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
     }
 }
 
+// Model EMA, timm's ModelEma.update in fp32: e' = fl(fl(e * d) + fl(w * o)) with o = (float)(1.0 - (double)decay) from the host.  Three roundings as torch's three
+// kernels make them.  The unit is built with -ffp-contract=fast, which lets the backend fuse any multiply with any add: this toolchain's __fmul_rn / __fadd_rn are
+// plain `*` / `+` and `#pragma clang fp contract(off)` does not reach the backend either (both forms came out as v_pk_mul + v_pk_fma: two roundings).  The empty asm
+// makes each product a value the combiner cannot look through; it emits no instruction.
+__device__ __forceinline__ float ema_lerp(float e, float w, float d, float o) {
+    float a = e * d, b = w * o;
+    asm("" : "+v"(a));
+    asm("" : "+v"(b));
+    return a + b;
+}
+
+// EMA = false is devias_adamw_multi as it always was (the descriptor's last word is not read); EMA = true also streams the shadow weights of every descriptor that has
+// some, from the updated parameter still in registers: +8 bytes per parameter instead of the 12 of a pass of its own.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const devias_opt_tensor* __restrict__ table, const int32_t* __restrict__ ct,
                                                           const int32_t* __restrict__ ci, float b1, float b2, float eps, float gscale,
-                                                          const float* __restrict__ gscale_dev) {
+                                                          const float* __restrict__ gscale_dev, float ema_d, float ema_o) {
     const devias_opt_tensor t = table[ct[blockIdx.x]];
     const int64_t lo = (int64_t)ci[blockIdx.x] * DEVIAS_OPT_CHUNK;
     const int64_t hi = lo + DEVIAS_OPT_CHUNK < t.n ? lo + DEVIAS_OPT_CHUNK : t.n;
@@ -268,18 +282,65 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const devias_opt_tenso
     };
     const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    // workgroup-uniform: this tensor's shadow, or none.  Its alignment is tested on its own: the float4 and the scalar form of `upd` contract differently, so a
+    // shadow that demoted the AdamW update to the scalar form would change the parameters' last bits; an unaligned shadow is read and written by dwords instead.
+    float* e = nullptr;
+    bool al_e = false;
+    if constexpr (EMA) {
+        if (t.ema) e = t.ema + lo;
+        al_e = (reinterpret_cast<uintptr_t>(e) & 15) == 0;
+    }
     int done = 0;
     if (al) {
         const int n4 = len >> 2;
         for (int i = threadIdx.x; i < n4; i += 256) {
             float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<const float4*>(g)[i];
             float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (EMA) {
+                if (e) ev = al_e ? reinterpret_cast<const float4*>(e)[i] : make_float4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
+            }
             upd(pv.x, gv.x, mv.x, vv.x); upd(pv.y, gv.y, mv.y, vv.y); upd(pv.z, gv.z, mv.z, vv.z); upd(pv.w, gv.w, mv.w, vv.w);
             reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
+            if constexpr (EMA) {
+                if (e) {
+                    ev.x = ema_lerp(ev.x, pv.x, ema_d, ema_o); ev.y = ema_lerp(ev.y, pv.y, ema_d, ema_o);
+                    ev.z = ema_lerp(ev.z, pv.z, ema_d, ema_o); ev.w = ema_lerp(ev.w, pv.w, ema_d, ema_o);
+                    if (al_e) reinterpret_cast<float4*>(e)[i] = ev;
+                    else { e[4 * i] = ev.x; e[4 * i + 1] = ev.y; e[4 * i + 2] = ev.z; e[4 * i + 3] = ev.w; }
+                }
+            }
         }
         done = n4 << 2;
     }
-    for (int i = done + threadIdx.x; i < len; i += 256) upd(p[i], g[i], m[i], v[i]);
+    for (int i = done + threadIdx.x; i < len; i += 256) {
+        upd(p[i], g[i], m[i], v[i]);
+        if constexpr (EMA) { if (e) e[i] = ema_lerp(e[i], p[i], ema_d, ema_o); }
+    }
+}
+
+// the shadow stream alone, over the same table and chunk lists: reads param and ema, writes ema; a descriptor without a shadow costs its workgroup one table read
+__global__ __launch_bounds__(256) void ema_multi_kernel(const devias_opt_tensor* __restrict__ table, const int32_t* __restrict__ ct,
+                                                        const int32_t* __restrict__ ci, float ema_d, float ema_o) {
+    const devias_opt_tensor t = table[ct[blockIdx.x]];
+    if (!t.ema) return;
+    const int64_t lo = (int64_t)ci[blockIdx.x] * DEVIAS_OPT_CHUNK;
+    const int64_t hi = lo + DEVIAS_OPT_CHUNK < t.n ? lo + DEVIAS_OPT_CHUNK : t.n;
+    const int len = (int)(hi - lo);
+    const float* p = t.param + lo; float* e = t.ema + lo;
+    int done = 0;
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(e)) & 15) == 0) {
+        const int n4 = len >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const float4 pv = reinterpret_cast<const float4*>(p)[i];
+            float4 ev = reinterpret_cast<const float4*>(e)[i];
+            ev.x = ema_lerp(ev.x, pv.x, ema_d, ema_o); ev.y = ema_lerp(ev.y, pv.y, ema_d, ema_o);
+            ev.z = ema_lerp(ev.z, pv.z, ema_d, ema_o); ev.w = ema_lerp(ev.w, pv.w, ema_d, ema_o);
+            reinterpret_cast<float4*>(e)[i] = ev;
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + threadIdx.x; i < len; i += 256) e[i] = ema_lerp(e[i], p[i], ema_d, ema_o);
 }
 
 inline int grid_for(int64_t n, int per_thread = 1) {
@@ -527,9 +588,36 @@ extern "C" int devias_adamw_multi(const devias_opt_tensor* table, const int32_t*
                                   const float* grad_scale_dev, void* stream) {
     DEVIAS_REQUIRE(table && chunk_tensor && chunk_index && n_chunks >= 0, "devias_adamw_multi: bad args");
     if (n_chunks == 0) return DEVIAS_OK;
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, beta1, beta2,
-                       eps, grad_scale, grad_scale_dev);
+    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, beta1, beta2,
+                       eps, grad_scale, grad_scale_dev, 0.f, 0.f);
     DEVIAS_CHECK_LAUNCH("devias_adamw_multi");
+    return DEVIAS_OK;
+}
+
+// the two factors of the shadow update: each in [0, 1] (a NaN fails both comparisons)
+static inline bool ema_factors_ok(float d, float o) { return d >= 0.f && d <= 1.f && o >= 0.f && o <= 1.f; }
+
+extern "C" int devias_adamw_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                                      int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
+                                      const float* grad_scale_dev, float ema_decay, float ema_one_minus_decay, void* stream) {
+    DEVIAS_REQUIRE(n_chunks >= 0 && (n_chunks == 0 || (table && chunk_tensor && chunk_index)), "devias_adamw_ema_multi: bad args");
+    DEVIAS_REQUIRE(ema_factors_ok(ema_decay, ema_one_minus_decay), "devias_adamw_ema_multi: decay %g / 1 - decay %g outside [0, 1]", (double)ema_decay,
+                   (double)ema_one_minus_decay);
+    if (n_chunks == 0) return DEVIAS_OK;
+    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, beta1, beta2,
+                       eps, grad_scale, grad_scale_dev, ema_decay, ema_one_minus_decay);
+    DEVIAS_CHECK_LAUNCH("devias_adamw_ema_multi");
+    return DEVIAS_OK;
+}
+
+extern "C" int devias_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
+                                float ema_decay, float ema_one_minus_decay, void* stream) {
+    DEVIAS_REQUIRE(n_chunks >= 0 && (n_chunks == 0 || (table && chunk_tensor && chunk_index)), "devias_ema_multi: bad args");
+    DEVIAS_REQUIRE(ema_factors_ok(ema_decay, ema_one_minus_decay), "devias_ema_multi: decay %g / 1 - decay %g outside [0, 1]", (double)ema_decay,
+                   (double)ema_one_minus_decay);
+    if (n_chunks == 0) return DEVIAS_OK;
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, ema_decay, ema_one_minus_decay);
+    DEVIAS_CHECK_LAUNCH("devias_ema_multi");
     return DEVIAS_OK;
 }
 

@@ -24,10 +24,12 @@ def train_class_batch(model, scene_model, samples, target, train_criterion, fg_m
     return total_loss, output, loss_dict
 
 
-def _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch, update_freq, grad_sync, check_finite_every):
+def _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch, update_freq, grad_sync, check_finite_every, model_ema=None):
     """The part of train_one_epoch that does not depend on the recipe (shared with engine_for_slot_hvu): LR/WD schedule poke, gradient accumulation over
     `update_freq` micro-batches, optional gradient all-reduce (`grad_sync`, devias_amd.parallel), clip + optimizer step, and one host check of the loss
-    every `check_finite_every` micro-batches.  `step(batch) -> (loss, loss_dict)` is the recipe: H2D copies, mask model, train_class_batch."""
+    every `check_finite_every` micro-batches.  `step(batch) -> (loss, loss_dict)` is the recipe: H2D copies, mask model, train_class_batch.
+    `model_ema` (devias_amd.ema.ModelEma) is updated after each optimizer step and only then (engine/engine_for_slot.py:154-155, 165-168): inside the fused
+    optimizer's launch where that is what steps, by `model_ema.update(model)` after any other optimizer."""
     optimizer.zero_grad(set_to_none=True)
     stats, grad_norm = {}, None
     for data_iter_step, batch in enumerate(data_loader):
@@ -53,12 +55,19 @@ def _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_sc
                 grad_sync.finish()
             if isinstance(optimizer, FusedAdamW) and optimizer.multi_tensor:
                 # gradient norm + clip_grad_norm_ (utils/utils.py:388-394) fused into the update; the norm stays on the device
-                optimizer.step(max_norm=float(max_norm or 0.0))
+                if model_ema is not None and model_ema.source is model and model_ema.on_device_of(model):
+                    optimizer.step(max_norm=float(max_norm or 0.0), ema=model_ema)
+                else:
+                    optimizer.step(max_norm=float(max_norm or 0.0))
+                    if model_ema is not None:                      # a shadow kept on the host (--model_ema_force_cpu), or of a wrapped model
+                        model_ema.update(model)
                 grad_norm = optimizer.last_grad_norm
             else:
                 if max_norm and max_norm > 0:
                     grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
                 optimizer.step()
+                if model_ema is not None:
+                    model_ema.update(model)
             optimizer.zero_grad(set_to_none=True)
         if check_finite_every and (data_iter_step + 1) % check_finite_every == 0:          # skipped batches only follow, so this counts the ones run
             loss_value = float(loss.detach().float().sum())
@@ -74,7 +83,7 @@ def _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_sc
 def train_one_epoch(model, scene_model, train_criterion, data_loader: Iterable, optimizer, device, epoch: int,
                     max_norm: float = 0, start_steps: int = 0, lr_schedule_values=None, wd_schedule_values=None,
                     num_training_steps_per_epoch: Optional[int] = None, update_freq: int = 1, mask_model=None,
-                    grad_sync=None, check_finite_every: int = 50, log_every: int = 100):
+                    grad_sync=None, check_finite_every: int = 50, log_every: int = 100, model_ema=None):
     """engine/engine_for_slot.py:64-214 restated for this stack: LR/WD schedule poke (:91-96), H2D (:98-99), mask model (:106-108), train_class_batch,
     backward, optional gradient all-reduce, optimizer step (_run_steps).  The per-step `loss.item()` finite check (:140-144) and
     `torch.cuda.synchronize()` (:171) are replaced by one host check every `check_finite_every` steps."""
@@ -92,7 +101,7 @@ def train_one_epoch(model, scene_model, train_criterion, data_loader: Iterable, 
         return loss, loss_dict
 
     return _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch,
-                      update_freq, grad_sync, check_finite_every)
+                      update_freq, grad_sync, check_finite_every, model_ema)
 
 
 def _evaluate(data_loader, model, device, n_fields, names, per_batch):

@@ -21,7 +21,7 @@ def train_class_batch(model, samples, action_targets, scene_targets, train_crite
 def train_one_epoch(model, train_criterion, data_loader: Iterable, optimizer, device, epoch: int,
                     max_norm: float = 0, start_steps: int = 0, lr_schedule_values=None, wd_schedule_values=None,
                     num_training_steps_per_epoch: Optional[int] = None, update_freq: int = 1, mask_model=None,
-                    grad_sync=None, check_finite_every: int = 50, log_every: int = 100):
+                    grad_sync=None, check_finite_every: int = 50, log_every: int = 100, model_ema=None):
     """engine/engine_for_slot_hvu.py:23-153 restated for this stack, with the keyword surface of engine_for_slot.train_one_epoch: batches are
     (samples, action_targets, scene_targets, ...) (:43); LR/WD schedule poke (:49-54), H2D (:56-58), mask model (:64-65; without one the
     masks are batch[3]), train_class_batch; backward, optional gradient all-reduce and optimizer step are engine_for_slot._run_steps.
@@ -39,7 +39,7 @@ def train_one_epoch(model, train_criterion, data_loader: Iterable, optimizer, de
         return loss, loss_dict
 
     return _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch,
-                      update_freq, grad_sync, check_finite_every)
+                      update_freq, grad_sync, check_finite_every, model_ema)
 
 
 def _validate(data_loader, model, device, action: bool, scene: bool, topk=(1, 5)):

@@ -752,3 +752,32 @@ def adamw_multi(table, chunk_tensor, chunk_index, beta1, beta2, eps, grad_scale=
         _chk(grad_scale_dev, "adamw_multi.grad_scale_dev", torch.float32)
     _lib.check(_lib.load().devias_adamw_multi(table.data_ptr(), chunk_tensor.data_ptr(), chunk_index.data_ptr(), chunk_tensor.numel(),
                                               beta1, beta2, eps, grad_scale, _p(grad_scale_dev), _stream()), "devias_adamw_multi")
+
+
+def ema_factors(decay: float):
+    """(decay, 1 - decay) as the two fp32 factors of the shadow update.  The second is `1. - decay` in double, rounded once: what torch computes for
+    `(1. - decay) * model_v`; 1.0f - fl32(decay) differs from it in the last bit for 0.9999 and 0.99."""
+    d = float(decay)
+    if not 0.0 <= d <= 1.0:                    # a NaN fails the comparison too
+        raise ValueError(f"model EMA decay must lie in [0, 1], got {decay!r}")
+    return d, 1.0 - d
+
+
+def adamw_ema_multi(table, chunk_tensor, chunk_index, beta1, beta2, eps, ema_decay, grad_scale=1.0, grad_scale_dev=None):
+    """devias_adamw_ema_multi: adamw_multi, and the shadow weights of every record whose `ema` word is set, in the same launch."""
+    _chk(table, "adamw_ema_multi.table", torch.uint8)
+    _chk(chunk_tensor, "adamw_ema_multi.chunk_tensor", torch.int32); _chk(chunk_index, "adamw_ema_multi.chunk_index", torch.int32)
+    if grad_scale_dev is not None:
+        _chk(grad_scale_dev, "adamw_ema_multi.grad_scale_dev", torch.float32)
+    d, o = ema_factors(ema_decay)
+    _lib.check(_lib.load().devias_adamw_ema_multi(table.data_ptr(), chunk_tensor.data_ptr(), chunk_index.data_ptr(), chunk_tensor.numel(),
+                                                  beta1, beta2, eps, grad_scale, _p(grad_scale_dev), d, o, _stream()), "devias_adamw_ema_multi")
+
+
+def ema_multi(table, chunk_tensor, chunk_index, ema_decay):
+    """devias_ema_multi: ema <- ema * decay + (1 - decay) * param for every record of the table whose `ema` word is set; reads nothing else of a record."""
+    _chk(table, "ema_multi.table", torch.uint8)
+    _chk(chunk_tensor, "ema_multi.chunk_tensor", torch.int32); _chk(chunk_index, "ema_multi.chunk_index", torch.int32)
+    d, o = ema_factors(ema_decay)
+    _lib.check(_lib.load().devias_ema_multi(table.data_ptr(), chunk_tensor.data_ptr(), chunk_index.data_ptr(), chunk_tensor.numel(), d, o, _stream()),
+               "devias_ema_multi")

@@ -17,6 +17,8 @@ xGMI is point-to-point (7 links/GPU); a few large buckets (default 64 MiB) keep 
 Reduction: fp32 SUM followed by a 1/world scale (exact mean of fp32 gradients) by default; `comm_dtype=torch.bfloat16` halves the
 bytes on the links (196.8 MB instead of 393.7 MB at ViT-B): gradients are rounded to bf16 once, RCCL sums them with bf16 partial
 results between ring steps, the mean is widened back into the fp32 bucket.  bench.py states which one it ran.
+Model EMA (devias_amd/ema.py) needs no communication: the gradients are all-reduced before the optimizer step, so every rank takes the same step from the same
+weights and its shadow weights stay identical to every other rank's.
 """
 from __future__ import annotations
 

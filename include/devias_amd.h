@@ -49,6 +49,8 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     170 = devias_option_name, option slot_mfma (additive),
                                     171 = devias_wgrad_group (+ devias_policy_wgrad_group_plan); devias_block_args grew by defer_wgrad / keep_dhpre / keep_dqkv / keep_dx1 / keep_g2 / keep_g1:
                                           a caller compiled against ABI <= 170 must zero-extend the struct (recompile),
+                                    172 = devias_adamw_ema_multi, devias_ema_multi; devias_opt_tensor.reserved became the shadow pointer `ema` (same size and offsets; additive:
+                                          devias_adamw_multi and devias_grad_sumsq_multi never read that word),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -500,6 +502,19 @@ int devias_adamw_step(float* param, const float* grad, float* exp_avg, float* ex
  *                            min(1, max_norm / (out[0] + 1e-6)) : 1   (clip_grad_norm_ semantics)
  *   devias_adamw_multi:      g' = g * grad_scale * (grad_scale_dev ? *grad_scale_dev : 1); AdamW update as devias_adamw_step
  * No host synchronisation anywhere: the clip coefficient stays on the device.
+ *
+ * Model EMA (ABI 172; timm's ModelEma.update as the reference's engines call it, engine/engine_for_slot.py:154-155, 165-168):
+ * per element, three single-rounded fp32 operations, no FMA:  e' = fl(fl(e * ema_decay) + fl(w * ema_one_minus_decay)).
+ * `ema_one_minus_decay` is the caller's (float)(1.0 - (double)decay), NOT 1.0f - ema_decay: torch evaluates `1. - decay` in double.
+ *   devias_adamw_ema_multi:  devias_adamw_multi, and where a descriptor's `ema` is not 0 also ema[i] <- e'(ema[i], updated param[i]) from the
+ *                            freshly updated value still in registers (36 bytes per parameter instead of 28 + 12 for a separate pass).  The parameters
+ *                            and moments come out bit-equal to devias_adamw_multi's whatever the shadow's alignment: a shadow that is not 16-byte
+ *                            aligned is accessed by dwords, it does not demote the update itself to the scalar form
+ *   devias_ema_multi:        the stand-alone stream over the same table and chunk lists: reads `param` and `ema` of descriptors whose `ema`
+ *                            is not 0, writes `ema`; never dereferences grad / exp_avg / exp_avg_sq (they may be 0).  Serves parameters that
+ *                            had no gradient this step, the per-tensor optimizer path and any other optimizer.
+ * Both validate before any launch: a null table or chunk list with n_chunks > 0, n_chunks < 0, a decay outside [0, 1] or NaN -> DEVIAS_EINVAL.
+ * A shadow must not overlap its parameter (the host side refuses that).
  * ------------------------------------------------------------------------------------------------- */
 #define DEVIAS_OPT_CHUNK 16384
 typedef struct {
@@ -509,7 +524,8 @@ typedef struct {
     float* exp_avg_sq;
     int64_t n;
     float lr, weight_decay, bc1, bc2_sqrt;   /* bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step) */
-    int64_t reserved;                         /* pads the descriptor to 64 bytes */
+    float* ema;                               /* ABI 172 (was `int64_t reserved`, the pad to 64 bytes): shadow weights of this tensor, 0 = none;
+                                                 read only by devias_adamw_ema_multi and devias_ema_multi */
 } devias_opt_tensor;
 int devias_grad_sumsq_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                             int32_t n_chunks, float* partials, void* stream);
@@ -517,6 +533,11 @@ int devias_clip_coef(const float* partials, int32_t n_chunks, float max_norm, fl
 int devias_adamw_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                        int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
                        const float* grad_scale_dev, void* stream);
+int devias_adamw_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                           int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
+                           const float* grad_scale_dev, float ema_decay, float ema_one_minus_decay, void* stream);
+int devias_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                     int32_t n_chunks, float ema_decay, float ema_one_minus_decay, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * FAME foreground masks and clip mixing (utils/transform/fame.py of the reference; CPU tensors + kornia there, called from
