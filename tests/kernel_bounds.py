@@ -1,4 +1,4 @@
-"""Per-element error bounds against float64 for the GEMM, LayerNorm and attention kernels, on graded inputs.
+"""Per-element error bounds against float64 for the GEMM, LayerNorm, attention (with and without dropout) and element-wise kernels, on graded inputs.
 
 A plain helper module (like grad_compare.py and golden_util.py): no fixtures, no plugin.  Everything here is torch arithmetic on whatever
 device the arguments live on -- float64 on the GPU in tests/test_kernel_bounds_gpu.py (none of this project's kernels), the CPU in
@@ -13,7 +13,7 @@ Unit roundoffs: u_bf16 = 2^-8, u_fp32 = 2^-24.   excess(out, ref, bound) = max |
 
 Each *_ref function returns (ref, bound) tensors of the output's shape (or a dict of such pairs).  One named term per rounding the
 kernel's design makes, nothing else:  (Kernel sources are cited by file name: gemm.hip, gemm_common.h, common.h, layernorm.hip, attn_fwd.hip, attn_mfma16.hip, attn_f32.hip,
-attn_bwd1w.hip live in devias_amd/csrc/, devias_amd.h is include/devias_amd.h.)
+attn_bwd1w.hip, attn_common.h, attention.hip, elementwise.hip live in devias_amd/csrc/, devias_amd.h is include/devias_amd.h.)
 
 GEMM (devias_gemm, every layout and kernel form; include/devias_amd.h "epilogue order")
     pre   = A B + bias                      fp32 accumulation, any order:     e_pre = (K + 8) u_fp32 (|A||B| + |bias|)
@@ -63,6 +63,33 @@ MHSA backward (include/devias_amd.h:256-277; dS = P o (dP - delta), delta = rows
     dbq / dbv (the _bias entry point): fp32 column sums over all B N rows (from the accumulators in bf16; dbv = colsum(dO) where
     devias_mhsa_bwd_bias_dv_from_do says so -- the same value, softmax rows sum to one).
 
+MHSA with dropout (attn_common.h:40-50: element (b, h, query, key) of the softmax matrix is kept when a hash of (seed, b H + h, i, j) is below keep 2^32, and kept
+elements are scaled by 1 / keep; oracle.ref_cpu.attn_drop_mask restates the hash, and its fp32 values widened are the `mask` of the references, 0 or 1 / keep.
+Never with the pre-scaled path: attention.hip:112 refuses it.)  With pm = p o mask:
+    forward   o = pm v; the probability that is rounded to bf16 for the P V product is the fp32 product p mask (attn_fwd.hip:146; fp32: attn_f32.hip:50), so
+              pv = pm |v|.  Row sums and lse are of the UN-dropped p: the lse reference and bound are unchanged.  A perturbation eps_j of score j moves o by
+              sum_j p_j eps_j (mask_j v_j - o): the score-rounding term is sum_j p_j T_j |mask_j v_jd - o_d|.  Otherwise the formula above.
+    backward  dP = mask o (dO v^T) (attn_mfma16.hip:315, 473-478; fp32: attn_f32.hip:111, 172), |dP| <= mask o (|dO| |v|^T); delta = rowsum(dO o o) from the stored
+              DROPPED o, with its masked forward bound; dS = p o (dP - delta); dV = pm^T dO with its propagated term built from pm; dQ, dK from that dS as before.
+              E keeps the plain path's term: the dropout dQ kernel and the two-wave dK / dV kernel round no operand, but the saved lse came from the forward's q c.
+              dbq / dbv: column sums as before, without the colsum(dO) alternative (under a mask it is no longer dbv); with option attn_bias_fused = 0 the sums are
+              taken from the stored dqkv (devias_colsum over its thirds): + u_out sum_rows |.|.
+    The slacks are those of attention without dropout; the dropout emulation needs less than they allow (table below).
+
+Element-wise kernels (devias_amd/csrc/elementwise.hip; all rigorous with factor 1 but act_bwd, which carries SLACK_ACT for its device transcendental)
+    mul_mask     y = a mask (+ b):  u_out |y| + 2 u_fp32 (|a mask| + |b|)         (the fp32 product and sum, :169-171)
+    row_scale, cast_scale   y = x s:  u_out |y| + u_fp32 |y|                       (one fp32 product, :36-39, :189)
+    add          u_out |y| + u_fp32 (|a| + |b|)                                     (:158-161)
+    act_bwd      sigmoid g y (1 - y) from the stored output: 3 u_fp32 |.|;  ReLU: exact;  GELU g gelu'(x) from the stored pre-activation: the dGELU term of the
+                 GEMM epilogue above (16 u_fp32 |g|, + DGELU_POLY_ERR |g| in bf16)    (:178-180)
+    colsum       out = beta out_old + sum_m x:  depth u_fp32 (sum|x| + |beta out_old|), depth = the longest chain of fp32 additions an addend goes through in
+                 the summation tree (:66-69, 76-132):  stage 1, per 256-row block: each of 8 row lanes adds its 32 rows in order (32), the 8 lane sums are added in
+                 order (8);  stage 2 (more than one block): each of 16 lanes adds every 16th block partial, ceil(ceil(M / 256) / 16) of them, and the 16 lane
+                 sums are added in order (16);  + 8 for beta out_old and its sum.  depth = 32 + 8 + ceil(ceil(M / 256) / 16) + 16 + 8.
+    rows_reduce_mod   one sequential chain per output (:139-141):  (M / mod + 1) u_fp32 sum|x|
+    cast, rows_broadcast, patch_im2col   exact: torch.equal against .to(dtype)
+    Inputs: graded over the flat index; for colsum and rows_reduce_mod the COLUMNS are graded and the rows are at one scale (columns_inputs).
+
 Constants.  The GEMM and LayerNorm-forward bounds are rigorous; their factor is 1.  The activation, LayerNorm-backward and attention bounds
 hold first-order arguments and a device transcendental: each carries ONE scalar slack on the whole bound, set so that the CPU emulation
 (the float64 reference plus exactly the named roundings, torch CPU arithmetic: tests/test_kernel_bounds_cpu.py) stays at <= 0.5 over all
@@ -76,6 +103,10 @@ kernels.  A bf16 output alone reaches ratio ~1 at slack 1 (u_bf16 is attained ne
     LayerNorm backward    2     dx 0.50 bf16, 0.15 fp32;  dgamma 0.02;  dbeta 0.02;  dx_colsum 0.002
     attention forward     1.4486  out 0.50 (bf16, pre-scaled q, logit std 6), 0.34 pre-scaled diffuse, 0.29 bf16 plain, 0.02 fp32;  lse 0.16
     attention backward    1.6086  dV 0.50 (bf16, pre-scaled q, logit std 6), dQ 0.24, dK 0.22;  plain path 0.10;  fp32 0.01;  dbq 0.01, dbv 0.08
+    attention dropout, fwd  1.4486  out 0.45 (bf16, keep 0.9, logit std 6), 0.29 keep 0.5, 0.03 fp32;  lse 0.16 (bf16), 0.01 fp32      (the slacks of attention: unchanged)
+    attention dropout, bwd  1.6086  dQ 0.07, dK 0.07, dV 0.12 (bf16, keep 0.5, logit std 6);  fp32 <= 0.01;  dbq 0.001, dbv 0.014;  from the stored tensor 0.002 / 0.015
+    element-wise            1     bf16 stores reach 0.88 - 1.00; fp32: mul_mask 0.45, add 0.49, row_scale 0.50, cast_scale 0.42;  colsum <= 0.015;  rows_reduce_mod 0.02
+    act_bwd                 2     sigmoid 0.49 bf16 / 0.31 fp32, GELU 0.48 / 0.07, ReLU 0 (exact)
 Each slack is twice what the emulation needs to stay at 1: 0.99 and 0.99 (a bf16 store: 2), 0.72422 -> 2 x 0.7243, 0.80425 -> 2 x 0.8043.
 
 Where this departs from the issue's "done when": it asks the emulation at <= 0.5 for EVERY operation.  Under the factor-1 bounds (GEMM without activation, aux_out,
@@ -386,55 +417,152 @@ def _attn_core(qkv, B, N, H, scale):
     return q, k, v, p, lse, T
 
 
-def mhsa_fwd_ref(qkv, B, N, H, scale, dtype, q_rounded=True):
+def mhsa_fwd_ref(qkv, B, N, H, scale, dtype, q_rounded=True, mask=None):
     """qkv: the values the kernels see, with the UNSCALED q (q' / c under DEVIAS_ATTN_Q_PRESCALED, then q_rounded = False: the rounding was the caller's).
+    mask: attention dropout, float64 [B, H, N, N] of 0 or 1 / keep (never with the pre-scaled path).
     {"out": (ref, bound) [B N, H 64], "lse": (ref, bound) [B, H, N]}"""
+    assert mask is None or q_rounded, "attention dropout is not offered with DEVIAS_ATTN_Q_PRESCALED"
     q, k, v, p, lse, T = _attn_core(qkv, B, N, H, scale)
     u = u_of(dtype)
     sr = 1.0 if (q_rounded or dtype == torch.float32) else 0.0
-    o = p @ v
-    pv = p @ v.abs()
+    pm = p if mask is None else p * mask
+    o = pm @ v
+    pv = pm @ v.abs()
     pT = (p * T).sum(-1)
     w = p * T
     wv = torch.empty_like(o)
     for d in range(64):
-        wv[..., d] = (w * (v[..., None, :, d] - o[..., :, None, d]).abs()).sum(-1)
+        vd = v[..., None, :, d] if mask is None else mask * v[..., None, :, d]
+        wv[..., d] = (w * (vd - o[..., :, None, d]).abs()).sum(-1)
     s = SLACK_ATTN_FWD
     b_o = s * (u * (o.abs() + pv + sr * wv) + 64 * U_FP32 * (pv + wv))
     b_l = s * (u * sr * pT + 64 * U_FP32 * (pT + 1.0) + 4 * U_FP32 * lse.abs())
     return {"out": (_rows(o, B, N, H), _rows(b_o, B, N, H)), "lse": (lse, b_l)}
 
 
-def mhsa_bwd_ref(qkv, d_o, B, N, H, scale, dtype, plain=True):
+def mhsa_bwd_ref(qkv, d_o, B, N, H, scale, dtype, plain=True, mask=None, bias_from_stored=False):
     """plain = False: the DEVIAS_ATTN_Q_PRESCALED path (qkv holds q' / c: the backward's scores ARE the forward's, no score term).
+    mask: attention dropout, float64 [B, H, N, N] of 0 or 1 / keep (plain path only).  bias_from_stored: dbq / dbv are column sums of the STORED dqkv
+    (option attn_bias_fused = 0 in bf16; the fp32 kernels always).
     {"dq", "dk", "dv"}: (ref, bound) [B N, H 64] each; {"dbq", "dbv"}: (ref, bound) [H 64]"""
+    assert mask is None or plain, "attention dropout is not offered with DEVIAS_ATTN_Q_PRESCALED"
     q, k, v, p, lse, T = _attn_core(qkv, B, N, H, scale)
     dO = _heads(d_o, B, N, H)
     u, f = u_of(dtype), 64 * U_FP32
     sr = 1.0 if (plain or dtype == torch.float32) else 0.0
-    fwd = mhsa_fwd_ref(qkv, B, N, H, scale, dtype, q_rounded=bool(sr))
+    fwd = mhsa_fwd_ref(qkv, B, N, H, scale, dtype, q_rounded=bool(sr), mask=mask)
     o, b_o = _heads(fwd["out"][0], B, N, H), _heads(fwd["out"][1], B, N, H)
     pT = (p * T).sum(-1, keepdim=True)
     E = u * sr * (T + pT) + f * (T + pT + 1.0)
     dP = dO @ v.transpose(-1, -2)
     aP = dO.abs() @ v.abs().transpose(-1, -2)
+    if mask is not None:
+        dP, aP, p_v = mask * dP, mask * aP, p * mask        # dP_ij = mask_ij (dO_i . v_j);  dV takes P o mask
+    else:
+        p_v = p
     delta = (dO * o).sum(-1, keepdim=True)
     e_delta = (dO.abs() * b_o).sum(-1, keepdim=True) + f * (dO * o).abs().sum(-1, keepdim=True)
     dS = p * (dP - delta)
     e_dS = p * ((E + u) * (dP - delta).abs() + f * aP + e_delta)
     s = SLACK_ATTN_BWD
-    dq, dk, dv = scale * (dS @ k), scale * (dS.transpose(-1, -2) @ q), p.transpose(-1, -2) @ dO
+    dq, dk, dv = scale * (dS @ k), scale * (dS.transpose(-1, -2) @ q), p_v.transpose(-1, -2) @ dO
     f_dq = scale * (e_dS @ k.abs()) + f * scale * (dS.abs() @ k.abs())
     f_dk = scale * (e_dS.transpose(-1, -2) @ q.abs()) + f * scale * (dS.abs().transpose(-1, -2) @ q.abs())
-    f_dv = ((E + u) * p).transpose(-1, -2) @ dO.abs() + f * (p.transpose(-1, -2) @ dO.abs())
+    f_dv = ((E + u) * p_v).transpose(-1, -2) @ dO.abs() + f * (p_v.transpose(-1, -2) @ dO.abs())
     out = {}
     for name, r, fp in (("dq", dq, f_dq), ("dk", dk, f_dk), ("dv", dv, f_dv)):
         out[name] = (_rows(r, B, N, H), _rows(s * (u * r.abs() + fp), B, N, H))
     col = (B * N / 128 + 128 + 8) * U_FP32
-    for name, r, fp, also in (("dbq", dq, f_dq, None), ("dbv", dv, f_dv, dO)):
+    stored = u if (bias_from_stored and dtype != torch.float32) else (U_FP32 if dtype == torch.float32 else 0.0)      # the sums are taken from the stored tensor
+    for name, r, fp, also in (("dbq", dq, f_dq, None), ("dbv", dv, f_dv, dO if mask is None else None)):      # (under a mask colsum(dO) is no longer dbv)
         rr, ff = _rows(r, B, N, H), _rows(fp, B, N, H)
-        bound = ff.sum(0) + (col + (U_FP32 if dtype == torch.float32 else 0.0)) * rr.abs().sum(0)
+        bound = ff.sum(0) + (col + stored) * rr.abs().sum(0)
         if also is not None:
             bound = bound + col * _rows(also, B, N, H).abs().sum(0)
         out[name] = (rr.sum(0), s * bound)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ element-wise kernels (devias_amd/csrc/elementwise.hip)
+def elementwise_inputs(n, dtype, seed=0, device="cpu", spread=6):
+    """[n] values graded over the flat index"""
+    return (_randn((n,), seed, device) * graded(n, spread, device).float()).to(dtype)
+
+
+def columns_inputs(M, N, dtype, seed=0, device="cpu", spread=6):
+    """[M, N] for the column / row-class sums: the COLUMNS graded, the rows at one scale -- a summed-away row then stands out at 1 / M of its column's sum against a
+    bound of ~depth 2^-24; with graded rows the fp32 summation's own allowance would hide it"""
+    return (_randn((M, N), seed, device) * graded(N, spread, device).float()[None, :]).to(dtype)
+
+
+def drop_mask(n, keep, seed=0, device="cpu"):
+    """an element-wise dropout mask as the model draws it: fp32 [n] of 0 or 1 / keep"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return ((torch.rand(n, generator=g) < keep).float() / torch.tensor(keep, dtype=torch.float32)).to(device)
+
+
+def mul_mask_ref(a, mask, b, dtype):
+    """y = a mask (+ b): the fp32 product and the fp32 sum round once each, against the sum of absolute terms (rigorous whether or not the compiler contracts
+    them into one FMA); one rounding of the output"""
+    am = a.double() * mask.double()
+    y, s_abs = (am, am.abs()) if b is None else (am + b.double(), am.abs() + b.double().abs())
+    e_mul, e_add = U_FP32 * s_abs, U_FP32 * s_abs
+    return y, u_of(dtype) * y.abs() + e_mul + e_add
+
+
+def row_scale_ref(x, scale, rows_per_scale, dtype):
+    """y = x scale[row / rows_per_scale]: one fp32 product, one rounding of the output"""
+    M = x.shape[0]
+    y = x.double() * scale.double().repeat_interleave(rows_per_scale)[:M, None]
+    return y, u_of(dtype) * y.abs() + U_FP32 * y.abs()
+
+
+def cast_scale_ref(src, scale, out_dtype):
+    """y = (out dtype)(src scale) with the fp32 value of `scale` the kernel is handed: one fp32 product, one rounding of the output"""
+    y = src.double() * float(torch.tensor(scale, dtype=torch.float32))
+    return y, u_of(out_dtype) * y.abs() + U_FP32 * y.abs()
+
+
+def add_ref(a, b, dtype):
+    y = a.double() + b.double()
+    return y, u_of(dtype) * y.abs() + U_FP32 * (a.double().abs() + b.double().abs())
+
+
+def act_bwd_ref(dy, y, act, dtype):
+    """devias_act_bwd: sigmoid dx = g y (1 - y) from the stored OUTPUT y (three fp32 roundings: 1 - y, and two products); ReLU dx = g [y > 0] (exact);
+    GELU dx = g gelu'(x) from the stored PRE-activation x (the dGELU term of gemm_ref).  Slack SLACK_ACT."""
+    g, v = dy.double(), y.double()
+    if act == ACT_SIGMOID:
+        r = g * v * (1.0 - v)
+        e = 3 * U_FP32 * r.abs()
+    elif act == ACT_RELU:
+        r = g * (v > 0).double()
+        e = torch.zeros_like(r)
+    elif act == ACT_GELU:
+        r = g * dgelu64(v)
+        e = (16 * U_FP32 if dtype == torch.float32 else DGELU_POLY_ERR + 16 * U_FP32) * g.abs()
+    else:
+        raise ValueError(act)
+    return r, SLACK_ACT * (u_of(dtype) * r.abs() + e)
+
+
+def colsum_depth(M):
+    """the longest chain of fp32 additions one addend of devias_colsum goes through (the tree is in the module docstring)"""
+    nparts = -(-M // 256)
+    return 32 + 8 + -(-nparts // 16) + 16 + 8
+
+
+def colsum_ref(x, beta=0.0, out_old=None):
+    """out[n] = beta out_old[n] + sum_m x[m, n], fp32 sums of the (exactly widened) inputs"""
+    x = x.double()
+    ref, s_abs = x.sum(0), x.abs().sum(0)
+    if beta != 0.0:
+        ref, s_abs = ref + beta * out_old.double(), s_abs + (beta * out_old.double()).abs()
+    return ref, colsum_depth(x.shape[0]) * U_FP32 * s_abs
+
+
+def rows_reduce_mod_ref(x, mod):
+    """out[r, n] = sum over the rows m = r (mod `mod`): one sequential fp32 chain of M / mod additions per output"""
+    M, N = x.shape
+    x = x.double().reshape(M // mod, mod, N)
+    return x.sum(0), (M // mod + 1) * U_FP32 * x.abs().sum(0)

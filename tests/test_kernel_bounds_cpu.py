@@ -1,7 +1,7 @@
 """The bounds of tests/kernel_bounds.py proved without a GPU: for every operation, on every generator, the ideal result (float64 rounded once) and the
 CPU emulation of the documented algorithm (the reference plus exactly the named roundings, torch CPU arithmetic) stay inside the bound, and every seeded
-mutant -- the errors hand-written kernels make -- exceeds it.  The last three tests record why the file exists: the maximum-norm `rel` metric of
-tests/test_kernels_gpu.py at its tolerance passes three of those mutants on graded inputs.
+mutant -- the errors hand-written kernels make -- exceeds it.  The last tests record why the file exists: the maximum-norm `rel` metric of
+tests/test_kernels_gpu.py at its tolerance passes those mutants on graded inputs (a flipped dropout-mask element among them).
 
 Limits: the ideal <= 1 everywhere; the emulation <= 1 under the rigorous bounds (GEMM without activation, LayerNorm forward: their factor is 1 and a bf16
 output rounding alone reaches ~1) and <= 0.5 under every bound that carries a slack (activations, LayerNorm backward, attention)."""
@@ -267,9 +267,10 @@ def b16(t):
     return t.float().to(BF).double()
 
 
-def attn_fwd_emul(qkv, B, N, H, dtype, prescaled=False, mutant=None):
+def attn_fwd_emul(qkv, B, N, H, dtype, prescaled=False, mutant=None, mask=None):
     """bf16: q' = bf16(q c) (or the caller's q'), S' = q' k in fp32, P = exp2(S' - m) rounded to bf16 for P V, l from the fp32 P, o rounded once.
-    fp32: the same in fp32 with no intermediate rounding.  Returns o [B N, H 64], lse [B, H, N]."""
+    fp32: the same in fp32 with no intermediate rounding.  mask (attention dropout, float64 [B, H, N, N] of 0 or 1 / keep): P mask is one fp32 product, rounded
+    once to bf16 for P V; l stays the sum of the un-dropped fp32 P.  Returns o [B N, H 64], lse [B, H, N]."""
     q, k, v = (t.double() for t in split(qkv, B, N, H))
     if dtype == BF:
         qs = q if prescaled else b16(f32(q * C))
@@ -287,7 +288,10 @@ def attn_fwd_emul(qkv, B, N, H, dtype, prescaled=False, mutant=None):
             mt = s[..., :k0 + 64].max(-1, keepdim=True).values
             l = f32(l + f32(torch.exp2(s[..., k0:k0 + 64] - mt)).sum(-1, keepdim=True))
         l = f32(l * torch.exp2(mt - m))
-    pb = b16(p) if dtype == BF else p
+    pd = p if mask is None else f32(p * mask)
+    if mutant == "l_from_the_dropped_p":                      # the normaliser (and lse) taken from the dropped probabilities
+        l = f32(pd.sum(-1, keepdim=True))
+    pb = b16(pd) if dtype == BF else pd
     o = f32(f32(pb @ v) / l)
     lse = f32((m + torch.log2(l)).squeeze(-1) / LOG2E)
     return rows(o, B, N, H).to(dtype), lse.float()
@@ -326,9 +330,10 @@ def test_attention_forward(mode, std, koff):
                     assert (idx % (AH * 64)) // 64 == 0, w(idx)                # the message names the head
 
 
-def attn_bwd_emul(qkv, o, d_o, lse, B, N, H, dtype, prescaled=False, mutant=None):
+def attn_bwd_emul(qkv, o, d_o, lse, B, N, H, dtype, prescaled=False, mutant=None, mask=None):
     """dQ kernel: scores from q' = bf16(q c); one-wave dK / dV kernel: scores from k' = bf16(k c) (plain path) -- with the flag both multiply the caller's q' and k.
-    P = exp2(S' - lse log2 e); dP = dO V^T; delta = rowsum(dO o) from the stored o; P and dS rounded to bf16 for their products; outputs rounded once."""
+    P = exp2(S' - lse log2 e); dP = dO V^T; delta = rowsum(dO o) from the stored o; P and dS rounded to bf16 for their products; outputs rounded once.
+    mask (attention dropout): dP is masked (one fp32 product) before dS, dV comes from bf16(P mask); the scores are those of the plain emulation."""
     q, k, v = (t.double() for t in split(qkv, B, N, H))
     dO = d_o.double().reshape(B, N, H, 64).permute(0, 2, 1, 3)
     oo = o.double().reshape(B, N, H, 64).permute(0, 2, 1, 3)
@@ -344,11 +349,13 @@ def attn_bwd_emul(qkv, o, d_o, lse, B, N, H, dtype, prescaled=False, mutant=None
         s_kv = f32(q @ r16(f32(k * C)).transpose(-1, -2))
         q_un = q
     dP = f32(dO @ v.transpose(-1, -2))
+    if mask is not None and mutant != "dp_left_unmasked":
+        dP = f32(dP * mask)
     delta = f32((dO * oo).sum(-1, keepdim=True))
     p_q, p_kv = f32(torch.exp2(s_q - lse2)), f32(torch.exp2(s_kv - lse2))
     dq = f32(SCALE * (r16(f32(p_q * (dP - delta))) @ k))
     dk = f32(SCALE * (r16(f32(p_kv * (dP - delta))).transpose(-1, -2) @ q_un))
-    dv = f32(r16(p_kv).transpose(-1, -2) @ dO)
+    dv = f32(r16(p_kv if mask is None else f32(p_kv * mask)).transpose(-1, -2) @ dO)
     # the bias gradients of the _bias entry point: fp32 column sums of the UNROUNDED dQ / dV accumulators (bf16: devias_amd.h:293-300; dbv = colsum(dO) on the one-wave path)
     dbq, dbv = f32(rows(dq, B, N, H).sum(0)), f32(rows(dv, B, N, H).sum(0))
     return tuple(rows(t, B, N, H).to(dtype) for t in (dq, dk, dv)) + (dbq.float(), dbv.float())
@@ -387,6 +394,176 @@ def test_attention_backward(mode, std, koff):
             kb.check("plain bound, " + name, t, *rp[name], w)
 
 
+# ------------------------------------------------------------------------------------------------ attention dropout
+DROP_SEED = 0x5DEECE66D1234567
+
+
+def drop_mask64(keep, B=AB, N=AN, H=AH, seed=DROP_SEED):
+    from oracle import ref_cpu
+    return ref_cpu.attn_drop_mask(keep, seed, B, H, N).double()
+
+
+def flip_in_the_small_head(mask, qkv, B, N, H):
+    """mutant (a): ONE mask element flipped (dropped <-> kept), in head 0 (V scaled 2^-6) of batch entry 0, at the last query and that row's most probable key"""
+    q, k, _ = (t.double() for t in split(qkv, B, N, H))
+    j = int(torch.argmax(q[0, 0, N - 1] @ k[0, 0].t()))
+    bad = mask.clone()
+    bad[0, 0, N - 1, j] = 0.0 if float(mask[0, 0, N - 1, j]) > 0 else float(mask.max())
+    return bad
+
+
+@pytest.mark.parametrize("std,koff", kb.ATTN_GENERATORS)
+@pytest.mark.parametrize("keep", [0.9, 0.5])
+@pytest.mark.parametrize("dtype", [F32, BF])
+def test_attention_dropout(dtype, keep, std, koff):
+    """forward and backward under the dropout mask of oracle.ref_cpu.attn_drop_mask: ideal <= 1, emulation <= 0.5, and the three mutants of a dropout kernel --
+    (a) one flipped mask element in the small head, (b) the normaliser taken from the dropped probabilities, (c) dP left unmasked in the backward -- exceed 1 on
+    the offset-free generators (reported on the key-offset one, whose bound's score term allows more: kernel_bounds.ATTN_GENERATORS)"""
+    qkv, d_o = kb.attention_inputs(AB, AN, AH, dtype, logit_std=std, seed=80, key_offset=koff)
+    mask = drop_mask64(keep)
+    assert set(torch.unique(mask).tolist()) == {0.0, float(torch.tensor(1.0) / torch.tensor(keep))}
+    w = lambda i: kb.where_attn(i, AN, AH)  # noqa: E731
+    tag = f"{dtype} keep {keep} std {std} koff {koff}"
+    rf = kb.mhsa_fwd_ref(qkv, AB, AN, AH, SCALE, dtype, mask=mask)
+    o, lse = attn_fwd_emul(qkv, AB, AN, AH, dtype, mask=mask)
+    report(f"mhsa dropout fwd ideal {tag}", kb.check("ideal", rf["out"][0].to(dtype), *rf["out"], w))
+    report(f"mhsa dropout fwd out emulation {tag}", kb.check("out", o, *rf["out"], w, limit=0.5))
+    report(f"mhsa dropout fwd lse emulation {tag}", kb.check("lse", lse, *rf["lse"], limit=0.5))
+    plain = kb.mhsa_fwd_ref(qkv, AB, AN, AH, SCALE, dtype)
+    assert torch.equal(rf["lse"][0], plain["lse"][0]) and torch.equal(rf["lse"][1], plain["lse"][1])          # lse: of the un-dropped p, reference and bound unchanged
+    rb = kb.mhsa_bwd_ref(qkv, d_o, AB, AN, AH, SCALE, dtype, mask=mask)
+    got = attn_bwd_emul(qkv, o, d_o, lse, AB, AN, AH, dtype, mask=mask)
+    for name, t in zip(("dq", "dk", "dv"), got[:3]):
+        report(f"mhsa dropout bwd {name} ideal {tag}", kb.check("ideal " + name, rb[name][0].to(dtype), *rb[name], w))
+        report(f"mhsa dropout bwd {name} emulation {tag}", kb.check(name, t, *rb[name], w, limit=0.5))
+    report(f"mhsa dropout bwd dbq emulation {tag}", kb.check("dbq", got[3], *rb["dbq"], limit=0.5))
+    report(f"mhsa dropout bwd dbv emulation {tag}", kb.check("dbv", got[4], *rb["dbv"], limit=0.5))
+    # attn_bias_fused = 0: the sums of the stored (rounded) thirds, and their bound
+    rs = kb.mhsa_bwd_ref(qkv, d_o, AB, AN, AH, SCALE, dtype, mask=mask, bias_from_stored=True)
+    for name, t in (("dbq", got[0]), ("dbv", got[2])):
+        report(f"mhsa dropout bwd {name} from the stored tensor {tag}", kb.check(name + " stored", f32(t.double().sum(0)).float(), *rs[name], limit=0.5))
+    # mutants
+    offset_free = koff == 0.0
+    om, _ = attn_fwd_emul(qkv, AB, AN, AH, dtype, mask=flip_in_the_small_head(mask, qkv, AB, AN, AH))
+    ra, idx = kb.excess(om, *rf["out"])
+    report(f"mhsa dropout mutant one flipped mask element {tag}", ra)
+    om, _ = attn_fwd_emul(qkv, AB, AN, AH, dtype, mask=mask, mutant="l_from_the_dropped_p")
+    rl = report(f"mhsa dropout mutant l from the dropped p {tag}", kb.excess(om, *rf["out"])[0])
+    bad = attn_bwd_emul(qkv, o, d_o, lse, AB, AN, AH, dtype, mask=mask, mutant="dp_left_unmasked")
+    rp = report(f"mhsa dropout mutant dP left unmasked {tag}", max(kb.excess(t, *rb[name])[0] for name, t in zip(("dq", "dk"), bad[:2])))
+    if offset_free:
+        assert ra > 1.0, (ra, w(idx))
+        row, col = divmod(idx, AH * 64)
+        assert (row, col // 64) == (AN - 1, 0), w(idx)                 # the message names the query and the head
+        assert rl > 1.0, rl
+        assert rp > 1.0, rp
+
+
+def test_the_mask_free_attention_references_are_unchanged():
+    """mask = None takes the code it always took; an all-ones mask (keep = 1) goes through the masked formulas and gives bitwise the same references and
+    bounds -- but for dbv, whose bound drops the colsum(dO) alternative under a mask"""
+    qkv, d_o = kb.attention_inputs(AB, AN, AH, BF, logit_std=6.0, seed=80)
+    ones = torch.ones(AB, AH, AN, AN, dtype=torch.float64)
+    a, b = kb.mhsa_fwd_ref(qkv, AB, AN, AH, SCALE, BF), kb.mhsa_fwd_ref(qkv, AB, AN, AH, SCALE, BF, mask=ones)
+    for k in ("out", "lse"):
+        assert torch.equal(a[k][0], b[k][0]) and torch.equal(a[k][1], b[k][1]), k
+    a, b = kb.mhsa_bwd_ref(qkv, d_o, AB, AN, AH, SCALE, BF), kb.mhsa_bwd_ref(qkv, d_o, AB, AN, AH, SCALE, BF, mask=ones)
+    for k in ("dq", "dk", "dv", "dbq", "dbv"):
+        assert torch.equal(a[k][0], b[k][0]), k
+        assert torch.equal(a[k][1], b[k][1]) or k == "dbv", k
+    assert bool((b["dbv"][1] < a["dbv"][1]).all())
+
+
+# ------------------------------------------------------------------------------------------------ element-wise kernels
+EW_N = 1027
+
+
+@pytest.mark.parametrize("dtype", [BF, F32])
+def test_elementwise_emulations(dtype):
+    """every element-wise reference against torch CPU fp32 arithmetic with exactly the named roundings: <= 1 under the rigorous bounds, <= 0.5 under SLACK_ACT"""
+    a, b = kb.elementwise_inputs(EW_N, dtype, seed=90), kb.elementwise_inputs(EW_N, dtype, seed=91)
+    mask = kb.drop_mask(EW_N, 0.9, seed=92)
+    af, bf_ = a.float(), b.float()
+    report(f"mul_mask emulation {dtype}", kb.check("mul_mask", (af * mask).to(dtype), *kb.mul_mask_ref(a, mask, None, dtype)))
+    report(f"mul_mask + b emulation {dtype}", kb.check("mul_mask + b", (af * mask + bf_).to(dtype), *kb.mul_mask_ref(a, mask, b, dtype)))
+    if dtype == BF:                                              # mutant: b added after the product was stored
+        assert kb.excess(((af * mask).to(BF).float() + bf_).to(BF), *kb.mul_mask_ref(a, mask, b, BF))[0] > 1.0
+    report(f"add emulation {dtype}", kb.check("add", (af + bf_).to(dtype), *kb.add_ref(a, b, dtype)))
+    x = kb.elementwise_inputs(300 * 764, dtype, seed=93).reshape(300, 764)
+    sc = torch.linspace(-1.5, 2.0, 43)
+    sc[3] = 0.0
+    report(f"row_scale emulation {dtype}", kb.check("row_scale", (x.float() * sc.repeat_interleave(7)[:300, None]).to(dtype), *kb.row_scale_ref(x, sc, 7, dtype)))
+    for sd, dd in ((F32, F32), (BF, F32), (F32, BF)):
+        if dtype == BF and (sd, dd) == (F32, F32):
+            continue
+        src = kb.elementwise_inputs(EW_N, sd, seed=94)
+        em = (src.float() * torch.tensor(1.0 / 3.0, dtype=F32)).to(dd)
+        report(f"cast_scale emulation {sd} -> {dd}", kb.check("cast_scale", em, *kb.cast_scale_ref(src, 1.0 / 3.0, dd)))
+    g = kb.elementwise_inputs(EW_N, dtype, seed=95)
+    pre = (kb._randn((EW_N,), 96, "cpu") * 1.5).to(dtype)
+    y = torch.sigmoid(pre.float()).to(dtype)
+    gf, yf, pf = g.float(), y.float(), pre.float()
+    report(f"act_bwd sigmoid emulation {dtype}", kb.check("sigmoid", (gf * yf * (1.0 - yf)).to(dtype), *kb.act_bwd_ref(g, y, kb.ACT_SIGMOID, dtype), limit=0.5))
+    report(f"act_bwd relu emulation {dtype}", kb.check("relu", torch.where(pf > 0, gf, torch.zeros_like(gf)).to(dtype), *kb.act_bwd_ref(g, pre, kb.ACT_RELU, dtype), limit=0.5))
+    report(f"act_bwd gelu emulation {dtype}", kb.check("gelu", act_emul(gf, pre, kb.ACT_DGELU, dtype).to(dtype), *kb.act_bwd_ref(g, pre, kb.ACT_GELU, dtype), limit=0.5))
+    # mutant: the derivative of the tanh form
+    t = math.sqrt(2 / math.pi) * (pf + 0.044715 * pf ** 3)
+    dtanh = 0.5 * (1 + torch.tanh(t)) + 0.5 * pf * (1 - torch.tanh(t) ** 2) * math.sqrt(2 / math.pi) * (1 + 3 * 0.044715 * pf * pf)
+    rt = report(f"act_bwd mutant tanh-form dGELU {dtype}", kb.excess((gf * dtanh).to(dtype), *kb.act_bwd_ref(g, pre, kb.ACT_GELU, dtype))[0])
+    if dtype == F32:                                             # (bf16: the polynomial's own allowance, 5.5e-4, is of the size of the tanh form's error -- reported)
+        assert rt > 1.0, rt
+    r = kb.columns_inputs(260, 40, dtype, seed=97)
+    report(f"rows_reduce_mod emulation {dtype}", kb.check("rows_reduce_mod", r.float().reshape(52, 5, 40).sum(0), *kb.rows_reduce_mod_ref(r, 5)))
+
+
+def colsum_emul(x, beta=0.0, out_old=None, mutant=None):
+    """the summation tree of devias_colsum in torch fp32: per 256-row block, lane ty sums rows ty, ty + 8, ... in order, the 8 lanes are added in order; the block
+    partials i, i + 16, ... are summed per lane and the 16 lanes in order; out = t + beta out_old"""
+    v = x.float()
+    if mutant == "sums_after_a_bf16_store":
+        v = v.to(BF).float()
+    M, N = v.shape
+    parts = []
+    for r0 in range(0, M, 256):
+        blk = v[r0:min(M, r0 + 256)]
+        if mutant == "last_row_dropped" and r0 + 256 >= M:
+            blk = blk[:-1]
+        t = torch.zeros(N)
+        for ty in range(8):
+            s = torch.zeros(N)
+            for row in blk[ty::8]:
+                s = s + row
+            t = t + s
+        parts.append(t)
+    if len(parts) == 1:
+        t = parts[0]
+    else:
+        t = torch.zeros(N)
+        for ly in range(16):
+            s = torch.zeros(N)
+            for part in parts[ly::16]:
+                s = s + part
+            t = t + s
+    return t + beta * out_old if beta != 0.0 else t
+
+
+@pytest.mark.parametrize("dtype", [BF, F32])
+@pytest.mark.parametrize("M", [1, 256, 257, 4097])
+def test_colsum_emulation_and_mutants(M, dtype):
+    N = 40
+    x = kb.columns_inputs(M, N, dtype, seed=98)
+    old = kb._randn((N,), 99, "cpu") * kb.graded(N, 6).float() * 4.0
+    for beta in (0.0, 1.0):
+        ref, bound = kb.colsum_ref(x, beta, old)
+        report(f"colsum emulation M {M} {dtype} beta {beta}", kb.check("colsum", colsum_emul(x, beta, old), ref, bound))
+    ref, bound = kb.colsum_ref(x)
+    rm = report(f"colsum mutant last row dropped M {M} {dtype}", kb.excess(colsum_emul(x, mutant="last_row_dropped"), ref, bound)[0])
+    assert rm > 1.0, rm
+    if dtype == F32:
+        rm = report(f"colsum mutant sums after a bf16 store M {M}", kb.excess(colsum_emul(x, mutant="sums_after_a_bf16_store"), ref, bound)[0])
+        assert rm > 1.0, rm
+
+
 # ------------------------------------------------------------------------------------------------ what the old metric misses
 OLD_TOL_GEMM = 2e-2 * 4            # test_kernels_gpu.py test_gemm_epilogues, bf16: TOL[bf16] * 4
 OLD_TOL_ATTN = 2e-2                # test_kernels_gpu.py test_mhsa_fwd_bwd, bf16 out
@@ -405,5 +582,17 @@ def test_the_old_metric_passes_a_dropped_key_in_the_small_head():
     r = kb.mhsa_fwd_ref(qkv, AB, AN, AH, SCALE, BF)
     good, _ = attn_fwd_emul(qkv, AB, AN, AH, BF)
     bad, _ = attn_fwd_emul(qkv, AB, AN, AH, BF, mutant="last_key_dropped_small_head")
+    assert rel(bad, r["out"][0]) < OLD_TOL_ATTN and abs(rel(bad, r["out"][0]) - rel(good, r["out"][0])) < 1e-6
+    assert kb.excess(bad, *r["out"])[0] > 1.0
+
+
+@pytest.mark.parametrize("keep", [0.9, 0.5])
+def test_the_old_metric_passes_a_flipped_mask_element_in_the_small_head(keep):
+    """test_mhsa_dropout_matches_the_reference_with_the_same_mask at its bf16 tolerance does not see one wrong mask element where V is small"""
+    qkv, _ = kb.attention_inputs(AB, AN, AH, BF, logit_std=1.0, seed=80)
+    mask = drop_mask64(keep)
+    r = kb.mhsa_fwd_ref(qkv, AB, AN, AH, SCALE, BF, mask=mask)
+    good, _ = attn_fwd_emul(qkv, AB, AN, AH, BF, mask=mask)
+    bad, _ = attn_fwd_emul(qkv, AB, AN, AH, BF, mask=flip_in_the_small_head(mask, qkv, AB, AN, AH))
     assert rel(bad, r["out"][0]) < OLD_TOL_ATTN and abs(rel(bad, r["out"][0]) - rel(good, r["out"][0])) < 1e-6
     assert kb.excess(bad, *r["out"])[0] > 1.0

@@ -1,4 +1,4 @@
-"""The accuracy anchor of the kernels (GPU only): every GEMM kernel form, LayerNorm and the attention kernels against float64 on graded inputs, each element
+"""The accuracy anchor of the kernels (GPU only): every GEMM kernel form, LayerNorm and the attention kernels (with and without dropout) against float64 on graded inputs, each element
 held to the first-order bound of tests/kernel_bounds.py (worst |out - ref| / bound <= 1).  The float64 references run in torch on the device: none of this
 project's kernels.  Every GEMM / attention call asserts through ops.counters() which kernel served it.  What no counter shows is not asserted: LayerNorm has none
 (one kernel family serves it), and none tells whether a persistent launch on static lists cut its tail tiles in thirds (option gemm_tail_split = 3 is set; the
@@ -301,3 +301,100 @@ def test_mhsa(B, N, H, mode, std, koff, options):
         ratios["dbq"] = kb.check("mhsa_bwd_bias dbq", dbq, *rb["dbq"])
         ratios["dbv"] = kb.check("mhsa_bwd_bias dbv", dbv, *rb["dbv"])
         say("mhsa_bwd", (B, N, H), f"{mode} std={std} koff={koff} attn_dkdv={form}", ratios)
+
+
+# the last two shapes have B H % 8 == 0 (the XCD-aware linear grid); (3, 130, 8) tells a swapped hidx % H / hidx / H apart.  The seed varies with the shape: two
+# are below 2^32 (s1 = 0), two have bit 63 set
+DROP_SHAPES = {(1, 64, 1): 0x01234567, (2, 100, 3): 0x5DEECE66D1234567, (1, 333, 1): 0x9E3779B97F4A7C15, (2, 321, 4): 0xFFFFFFFF, (3, 130, 8): 0x8000000000000001}
+
+
+def _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt, bias=True):
+    """forward, backward and (bias) the backward through the _bias entry point with pre-filled destinations (they are overwritten); counters asserted on each"""
+    D = H * 64
+    (out, lse), _ = served(o, lambda: o.mhsa_fwd(qkv, B, N, H, SCALE, drop=drop), **fcnt)
+    dqkv, _ = served(o, lambda: o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, SCALE, drop=drop), **bcnt)
+    if not bias:
+        return out, lse, dqkv
+    dbq, dbv = torch.full((D,), 7.0, device=DEV), torch.full((D,), -3.0, device=DEV)
+    dqkv2, _ = served(o, lambda: o.mhsa_bwd(qkv, out, d_o, lse, B, N, H, SCALE, drop=drop, bias_out=(dbq, dbv)), **bcnt)
+    assert torch.equal(dqkv2, dqkv)
+    return out, lse, dqkv, dbq, dbv
+
+
+@pytest.mark.parametrize("std,koff", kb.ATTN_GENERATORS)
+@pytest.mark.parametrize("keep", [0.9, 0.5])
+@pytest.mark.parametrize("dtype", [F32, BF])
+@pytest.mark.parametrize("B,N,H", list(DROP_SHAPES))
+def test_mhsa_dropout(B, N, H, dtype, keep, std, koff, options):
+    """attention dropout (the DROP instantiations of the four-wave forward, the <2, 4> dQ and the two-wave dK / dV kernel, and of the three fp32 kernels) under the
+    mask of oracle.ref_cpu.attn_drop_mask: out, lse, dQ, dK, dV and the bias gradients (from the accumulators, and with attn_bias_fused = 0 from the stored tensor)
+    within their float64 bounds; bitwise the same under the plain 3-D grid (attn_xcd = 0) where the XCD-aware one serves, under every attn_cfg, and run to run"""
+    from oracle import ref_cpu
+    o = options
+    for name, v in (("attn_dkdv", 1), ("attn_xcd", 1), ("attn_cfg", 0), ("attn_bias_fused", 1)):
+        o.set_option(name, v)
+    seed = DROP_SHAPES[(B, N, H)]
+    drop = (keep, seed)
+    qkv, d_o = kb.attention_inputs(B, N, H, dtype, logit_std=std, seed=1100, device=DEV, key_offset=koff)
+    mask = ref_cpu.attn_drop_mask(keep, seed, B, H, N).to(DEV).double()
+    where = lambda i: kb.where_attn(i, N, H)  # noqa: E731
+    D = H * 64
+    if dtype == F32:
+        fcnt, bcnt = {"mhsa_fwd_f32": 1, "mhsa_fwd_bf16": 0}, {"mhsa_bwd_f32": 1, "mhsa_bwd_bf16": 0}
+    else:                    # dropout overrides attn_dkdv = 1: the two-wave dK / dV kernel
+        fcnt, bcnt = {"mhsa_fwd_bf16": 1, "mhsa_qpre": 0}, {"mhsa_bwd_bf16": 1, "mhsa_qpre": 0, "dkdv2w": 1, "dkdv1w": 0, "dkdv1w_rest": 0}
+    tag = f"{dtype} keep={keep} std={std} koff={koff}"
+    out, lse, dqkv, dbq, dbv = _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt)
+    rf = kb.mhsa_fwd_ref(qkv, B, N, H, SCALE, dtype, mask=mask)
+    say("mhsa_dropout fwd", (B, N, H), tag, {"out": kb.check("mhsa_fwd_dropout out", out, *rf["out"], where), "lse": kb.check("mhsa_fwd_dropout lse", lse, *rf["lse"])})
+    rb = kb.mhsa_bwd_ref(qkv, d_o, B, N, H, SCALE, dtype, mask=mask)
+    g = dqkv.reshape(B * N, 3, D)
+    ratios = {name: kb.check(f"mhsa_bwd_dropout {name}", g[:, i].contiguous(), *rb[name], where) for i, name in enumerate(("dq", "dk", "dv"))}
+    ratios["dbq"] = kb.check("mhsa_bwd_bias dbq (dropout)", dbq, *rb["dbq"])
+    ratios["dbv"] = kb.check("mhsa_bwd_bias dbv (dropout)", dbv, *rb["dbv"])
+    with o.options(attn_bias_fused=0):                    # the strided devias_colsum over the dQ and dV thirds of the stored dqkv
+        _, _, dqkv_s, dbq_s, dbv_s = _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt)
+    assert torch.equal(dqkv_s, dqkv)
+    rs = kb.mhsa_bwd_ref(qkv, d_o, B, N, H, SCALE, dtype, mask=mask, bias_from_stored=True)
+    ratios["dbq_stored"] = kb.check("mhsa_bwd_bias dbq (dropout, attn_bias_fused 0)", dbq_s, *rs["dbq"])
+    ratios["dbv_stored"] = kb.check("mhsa_bwd_bias dbv (dropout, attn_bias_fused 0)", dbv_s, *rs["dbv"])
+    say("mhsa_dropout bwd", (B, N, H), tag, ratios)
+    first = (out, lse, dqkv, dbq, dbv)
+    if (B * H) % 8 == 0:                                  # "Same bits" on either grid (attn_common.h head_map)
+        with o.options(attn_xcd=0):
+            again = _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt)
+        for name, a, b in zip(("out", "lse", "dqkv", "dbq", "dbv"), first, again):
+            assert torch.equal(a, b), f"attn_xcd 0 / 1 differ in {name}"
+    if (B, N, H) == (2, 100, 3):                          # under p.drop only one kernel form exists
+        for cfg in (1, 2, 3, 6, 7):
+            with o.options(attn_cfg=cfg):
+                again = _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt, bias=False)
+            for name, a, b in zip(("out", "lse", "dqkv"), first, again):
+                assert torch.equal(a, b), f"attn_cfg {cfg} / 0 differ in {name}"
+    # run to run: the mask is a function of the seed
+    again = _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt)
+    for name, a, b in zip(("out", "lse", "dqkv", "dbq", "dbv"), first, again):
+        assert torch.equal(a, b), f"two runs with the same seed differ in {name}"
+    out_next, _ = o.mhsa_fwd(qkv, B, N, H, SCALE, drop=(keep, seed + 1))
+    assert not torch.equal(out_next, out)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF])
+@pytest.mark.parametrize("B,N,H", [(2, 100, 3), (2, 321, 4)])
+def test_mhsa_dropout_keep_one_is_no_dropout(B, N, H, dtype, options):
+    """drop = (1.0, seed): the plain kernels serve (by counters: under attn_dkdv = 1 the one-wave dK / dV kernel, under 0 the two-wave one) and give bitwise the
+    results of the entry points without dropout under the same option value"""
+    o = options
+    qkv, d_o = kb.attention_inputs(B, N, H, dtype, logit_std=6.0, seed=1200, device=DEV)
+    drop = (1.0, DROP_SHAPES[(B, N, H)])
+    for form in ((1, 0) if dtype == BF else (1,)):
+        o.set_option("attn_dkdv", form)
+        if dtype == F32:
+            fcnt, bcnt = {"mhsa_fwd_f32": 1}, {"mhsa_bwd_f32": 1}
+        else:
+            fcnt = {"mhsa_fwd_bf16": 1}
+            bcnt = {"mhsa_bwd_bf16": 1, "dkdv1w": int(form == 1 and N >= 256), "dkdv1w_rest": int(form == 1 and N % 256 > 0), "dkdv2w": int(form == 0)}
+        out, lse, dqkv, dbq, dbv = _drop_run(o, qkv, d_o, B, N, H, drop, fcnt, bcnt)
+        out_p, lse_p, dqkv_p, dbq_p, dbv_p = _drop_run(o, qkv, d_o, B, N, H, None, fcnt, bcnt)
+        for name, a, b in zip(("out", "lse", "dqkv", "dbq", "dbv"), (out, lse, dqkv, dbq, dbv), (out_p, lse_p, dqkv_p, dbq_p, dbv_p)):
+            assert torch.equal(a, b), f"keep = 1 differs from the plain entry point in {name} (attn_dkdv {form})"
