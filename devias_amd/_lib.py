@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 172                # devias_version() of the library these prototypes describe
+ABI_VERSION = 173                # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -180,6 +180,8 @@ PROTOTYPES = {
     "devias_encoder_block_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I, _I]),
     "devias_encoder_block_fwd": (c_int, [POINTER(BlockArgs), _P, _P, _P]),
     "devias_encoder_block_bwd": (c_int, [POINTER(BlockArgs), _P, _P, _P, POINTER(BlockGrads), _P, _L, _P]),
+    "devias_encoder_block_infer_workspace_bytes": (c_int64, [_I, _I, _L, _I, _I, _I, _I]),
+    "devias_encoder_block_infer": (c_int, [POINTER(BlockArgs), _P, _P, _L, _P]),
     "devias_head_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I, _I, _I]),
     "devias_head_save_bytes": (c_int64, [_I, _I, _I, _I, _I]),
     "devias_head_fwd": (c_int, [POINTER(HeadArgs), _P, _P, _P, _P, _P]),
@@ -200,7 +202,7 @@ PROTOTYPES = {
 COUNTERS = {"gemm128_f32": 0, "gemm128_bf16": 1, "gemm_ss": 2, "gemm256": 3, "gemm256p": 4, "splitk_reduce": 5,
             "mhsa_fwd_bf16": 6, "mhsa_bwd_bf16": 7, "mhsa_fwd_f32": 8, "mhsa_bwd_f32": 9, "mhsa_bwd_fused": 10, "gemm_sk": 11, "gemm256w": 12, "gemm_smallm": 13, "gemm256d": 14,
             "dkdv1w": 15, "dkdv1w_pers": 16, "dkdv1w_rest": 17, "dkdv2w": 18, "mhsa_qpre": 19, "loss_labels": 20,
-            "slotm": 21, "slotf_valu": 22, "slot": 23}     # DEVIAS_CNT_*
+            "slotm": 21, "slotf_valu": 22, "slot": 23, "block_infer": 24}     # DEVIAS_CNT_*
 OPT_CHUNK = 16384          # DEVIAS_OPT_CHUNK
 OPT_TENSOR_BYTES = 64      # sizeof(devias_opt_tensor)
 

@@ -4,6 +4,7 @@
 // 55 ms device step, and eight such processes share one host on an 8-GPU node.  With these entry points a step is ~40 host -> library calls.
 //
 //   devias_encoder_block_fwd/bwd   Block.forward of model/modeling_slot.py:142-152 (LN -> QKV -> MHSA -> proj+res -> LN -> fc1+GELU -> fc2+res)
+//   devias_encoder_block_infer     the same block's forward where nobody will ask for a backward (evaluation, the frozen teacher): no arena, one workspace
 //   devias_agg_block_fwd/bwd       final LayerNorm + AggregationBlock, folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:120-139;
 //                                  agg_block/attention.py:32-40,120-141)
 //   devias_head_fwd/bwd            shared head + MaskPredictor (modeling_slot.py:392-393, 194-216)
@@ -147,13 +148,41 @@ struct BlockScratch {
 };
 // forward ran the qkv GEMM on the caller's q-scaled copies (ABI 167): bf16, both pointers given
 inline bool block_qpre(const devias_block_args* a) { return a->dtype == DEVIAS_BF16 && a->WqkvS && a->qkv_biasS; }
-int block_check(const devias_block_args* a, const char* who) {
+// Forward-only block (devias_encoder_block_infer): every intermediate in the caller's workspace, nothing kept.  `rows` >= B * N rows of u / qkv / o / x1 / hact (the
+// teacher's token matrix is zero-padded to whole 256-row tiles); ONE pair of LayerNorm statistics (both LayerNorms write it, nobody reads it); the lse the attention
+// entry point requires; the GEMMs' own workspace (small-M split-K slabs) behind them.
+struct BlockInferWs {
+    char *u, *qkv, *o, *x1, *hact;      // u is reused for u2
+    float *mean, *rstd, *lse, *kws;      // kws: the GEMMs' own workspace
+    int64_t kws_bytes, bytes;
+    BlockInferWs(void* base, int B, int N, int64_t rows, int D, int H, int hid, int dtype) {
+        const int64_t es = esize(dtype);
+        int64_t off = 0;
+        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
+        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
+        u = take(rows * D * es); qkv = take(rows * 3 * D * es); o = take(rows * D * es); x1 = take(rows * D * es); hact = take(rows * hid * es);
+        mean = (float*)take(rows * 4); rstd = (float*)take(rows * 4);
+        lse = (float*)take((int64_t)B * H * N * 4);
+        const int M = (int)rows;
+        kws_bytes = al256(max64(max64(gemm_ws(M, 3 * D, D, 0), gemm_ws(M, D, D, 0)), max64(gemm_ws(M, hid, D, 0), gemm_ws(M, D, hid, 0)))) + 256;
+        kws = (float*)take(kws_bytes);
+        bytes = off;
+    }
+};
+inline bool infer_dims_ok(int32_t B, int32_t N, int64_t rows, int32_t D, int32_t H, int32_t hid) {
+    return B > 0 && N > 0 && D > 0 && H > 0 && hid > 0 && rows >= (int64_t)B * N && rows <= 0x7fffffff;
+}
+int block_check(const devias_block_args* a, const char* who, bool need_save = true) {
     DEVIAS_REQUIRE(a, "%s: null args", who);
     DEVIAS_REQUIRE(a->B > 0 && a->N > 0 && a->D > 0 && a->H > 0 && a->hidden > 0 && a->D == a->H * 64, "%s: bad dims (B=%d N=%d D=%d H=%d hidden=%d; head dim must be 64)", who,
                    a->B, a->N, a->D, a->H, a->hidden);
     DEVIAS_REQUIRE(a->dtype == DEVIAS_BF16 || a->dtype == DEVIAS_F32, "%s: bad dtype %d", who, a->dtype);
     DEVIAS_REQUIRE(a->n1w && a->n1b && a->n2w && a->n2b && a->Wqkv && a->Wp && a->W1 && a->W2 && a->qkv_bias && a->pb && a->b1 && a->b2, "%s: null parameter", who);
     DEVIAS_REQUIRE((a->WqkvS != nullptr) == (a->qkv_biasS != nullptr) && (!a->WqkvS || a->dtype == DEVIAS_BF16), "%s: WqkvS and qkv_biasS go together (bf16 only)", who);
+    if (!need_save) {          // the forward-only block: no arena, and a workspace of its own size (checked by the caller, which knows `rows`)
+        DEVIAS_REQUIRE(a->ws && aligned16(a->ws), "%s: ws must be 16-byte aligned, non-null", who);
+        return DEVIAS_OK;
+    }
     DEVIAS_REQUIRE(a->save && a->ws && aligned16(a->save) && aligned16(a->ws), "%s: save / ws must be 16-byte aligned, non-null", who);
     DEVIAS_REQUIRE(a->ws_bytes >= devias_encoder_block_workspace_bytes(a->B, a->N, a->D, a->H, a->hidden, a->dtype), "%s: workspace too small", who);
     return DEVIAS_OK;
@@ -194,6 +223,46 @@ extern "C" int devias_encoder_block_fwd(const devias_block_args* a, const void* 
     RUN(ln_fwd(c, s.x1, a->n2w, a->n2b, s.u2, s.mean2, s.rstd2, M, D, a->eps));
     { Epi e; e.bias = a->b1; e.act = DEVIAS_ACT_GELU; e.aux_out = s.hpre; RUN(gemm(c, s.u2, a->W1, s.hact, M, hid, D, D, D, 0, 0, e)); }
     { Epi e; e.bias = a->b2; e.res = s.x1; e.row_scale = a->ds2; e.rows_per_scale = N; RUN(gemm(c, s.hact, a->W2, x2, M, D, hid, hid, hid, 0, 0, e)); }  // x1 + drop_path(mlp(.))
+    return DEVIAS_OK;
+}
+
+// ---- the forward nobody differentiates (ABI 173): evaluation of the student, the frozen teacher inside a training step -----------------------------------------------
+// The launches of devias_encoder_block_fwd in its order, minus what only backward reads: no arena (every intermediate in `ws`, one buffer for all blocks of a
+// model), fc1 with ONE output (no saved pre-activation: the call has no compile-time epilogue in pers_launch and runs the generic form).  x2 is bitwise the training forward's.
+extern "C" int64_t devias_encoder_block_infer_workspace_bytes(int32_t B, int32_t N, int64_t rows, int32_t D, int32_t H, int32_t hidden, int32_t dtype) {
+    if (!infer_dims_ok(B, N, rows, D, H, hidden)) return 0;
+    return BlockInferWs(nullptr, B, N, rows, D, H, hidden, dtype).bytes;
+}
+
+extern "C" int devias_encoder_block_infer(const devias_block_args* a, const void* x, void* x2, int64_t rows, void* stream) {
+    const char* who = "devias_encoder_block_infer";
+    RUN(block_check(a, who, false));
+    DEVIAS_REQUIRE(!a->ds1 && !a->ds2 && !a->defer_wgrad && !a->keep_dhpre && !a->keep_dqkv && !a->keep_dx1 && !a->keep_g2 && !a->keep_g1,
+                   "%s: ds1 / ds2 / defer_wgrad / keep_* are training arguments and must be zero", who);
+    DEVIAS_REQUIRE(x && x2 && x != x2 && aligned16(x) && aligned16(x2), "%s: x / x2 must be two different 16-byte aligned buffers", who);
+    const int B = a->B, N = a->N, D = a->D, H = a->H, hid = a->hidden;
+    DEVIAS_REQUIRE(infer_dims_ok(B, N, rows, D, H, hid), "%s: rows = %lld must be in [B * N = %lld, 2^31)", who, (long long)rows, (long long)B * N);
+    DEVIAS_REQUIRE(a->ws_bytes >= devias_encoder_block_infer_workspace_bytes(B, N, rows, D, H, hid, a->dtype), "%s: workspace too small", who);
+    const int M = (int)rows;
+    const int64_t real = (int64_t)B * N, es = esize(a->dtype);
+    const BlockInferWs s(a->ws, B, N, rows, D, H, hid, a->dtype);
+    const Ctx c{a->dtype, s.kws, s.kws_bytes, nullptr, 0, stream};
+    devias_range r("encoder_block_infer");
+    devias_count(DEVIAS_CNT_BLOCK_INFER);
+    RUN(ln_fwd(c, x, a->n1w, a->n1b, s.u, s.mean, s.rstd, M, D, a->eps));
+    const bool qpre = block_qpre(a);
+    { Epi e; e.bias = qpre ? a->qkv_biasS : a->qkv_bias; RUN(gemm(c, s.u, qpre ? a->WqkvS : a->Wqkv, s.qkv, M, 3 * D, D, D, D, 0, 0, e)); }
+    if (rows > real) {          // the attention writes the first B * N rows of o; the pad rows the projection multiplies are zero in every call, whatever the workspace held
+        if (hipMemsetAsync(s.o + real * D * es, 0, (size_t)((rows - real) * D * es), (hipStream_t)stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return devias_set_error(DEVIAS_ELAUNCH, "%s: cannot zero the pad rows of o", who);
+        }
+    }
+    RUN(devias_mhsa_fwd_flags(s.qkv, s.o, s.lse, B, N, H, 0.125f, a->dtype, qpre ? DEVIAS_ATTN_Q_PRESCALED : 0, stream));
+    { Epi e; e.bias = a->pb; e.res = x; RUN(gemm(c, s.o, a->Wp, s.x1, M, D, D, D, D, 0, 0, e)); }
+    RUN(ln_fwd(c, s.x1, a->n2w, a->n2b, s.u, s.mean, s.rstd, M, D, a->eps));
+    { Epi e; e.bias = a->b1; e.act = DEVIAS_ACT_GELU; RUN(gemm(c, s.u, a->W1, s.hact, M, hid, D, D, D, 0, 0, e)); }
+    { Epi e; e.bias = a->b2; e.res = s.x1; RUN(gemm(c, s.hact, a->W2, x2, M, D, hid, hid, hid, 0, 0, e)); }
     return DEVIAS_OK;
 }
 

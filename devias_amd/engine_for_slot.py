@@ -4,9 +4,11 @@ reference) or precomputed scene logits (the primary benchmark metric treats them
 from __future__ import annotations
 
 import math
+import os
 import sys
 from typing import Iterable, Optional
 
+import numpy as np
 import torch
 
 from .optim import FusedAdamW
@@ -156,3 +158,65 @@ def final_test(data_loader, model, device, file):
     with open(file, "w") as f:
         f.writelines(lines)
     return stats
+
+
+@torch.no_grad()
+def final_test_with_scene_label(data_loader, model, scene_model, device, file, num_labels=400):
+    """engine/engine_for_slot.py:310-367, the `--eval --eval_scene` mode: the logits of the selected SCENE slot, cut to the scene classes `[:, num_labels:]` of the
+    unified head, against the frozen teacher's argmax as the target.  Writes the reference's file -- a first line with the LAST batch's `acc1, acc5` (the reference
+    formats the two 0-d tensors timm's `accuracy` returns; so does this), then one line `id [logits] target chunk split` per sample -- and returns
+    {'loss', 'acc1', 'acc5'} as sample-weighted means (acc in percent)."""
+    scene_model.eval()
+    first, lines = ["0.0, 0.0\n"], []
+
+    def per_batch(out, fields, batch):
+        output = out[1][1].float()[:, num_labels:]
+        target = torch.argmax(scene_model(fields[0], return_attn=False)[1], dim=1)
+        m = _batch_metrics(output, target, (1, 5))
+        n = output.shape[0]
+        first[0] = "{}, {}\n".format(m[2].float() * 100. / n, m[3].float() * 100. / n)
+        rows, tgt = output.cpu().numpy(), target.cpu().numpy()
+        for i, (sample_id, chunk_nb, split_nb) in enumerate(zip(*batch[2:5])):
+            lines.append("{} {} {} {} {}\n".format(sample_id, str(rows[i].tolist()), str(int(tgt[i])), str(int(chunk_nb)), str(int(split_nb))))
+        return m
+
+    stats = _evaluate(data_loader, model, device, 1, ["acc1", "acc5"], per_batch)
+    with open(file, "w") as f:
+        f.writelines(first + lines)
+    return stats
+
+
+def merge(eval_path, num_tasks):
+    """engine/engine_for_slot.py:370-419, the multi-view vote every reported test accuracy goes through: reads `0.txt` ... `(num_tasks - 1).txt` as written by
+    final_test / final_test_with_scene_label, takes the softmax of every view, drops a repeated (chunk, split) of a video (the first one stays; the key is the
+    reference's, the two numbers' digits joined), averages the views of a video and returns (top-1, top-5) in percent.  A video's label is that of its last kept
+    view.  Vectorised numpy in the calling process: one softmax over all views, one segmented sum over the views sorted by video (the reference maps a pool of 64
+    processes over the videos)."""
+    index, seen, vid, label, feats = {}, set(), [], [], []
+    for x in range(num_tasks):
+        with open(os.path.join(eval_path, str(x) + ".txt"), "r") as f:
+            rows = f.readlines()[1:]
+        for line in rows:
+            line = line.strip()
+            name, rest = line.split("[")[0], line.split("]")[1].split(" ")
+            v = index.setdefault(name, len(index))
+            if len(label) <= v:
+                label.append(0)
+            if (v, rest[2] + rest[3]) in seen:
+                continue
+            seen.add((v, rest[2] + rest[3]))
+            label[v] = int(rest[1])
+            vid.append(v)
+            feats.append(np.array(line.split("[")[1].split("]")[0].split(","), dtype=np.float64))
+    if not vid:
+        return float("nan"), float("nan")
+    z = np.stack(feats)
+    z = np.exp(z - z.max(axis=1, keepdims=True))
+    p = z / z.sum(axis=1, keepdims=True)
+    vid, label = np.asarray(vid), np.asarray(label)
+    order = np.argsort(vid, kind="stable")
+    counts = np.bincount(vid, minlength=len(index))
+    mean = np.add.reduceat(p[order], np.concatenate(([0], np.cumsum(counts)[:-1])), axis=0) / counts[:, None]
+    top5 = np.argsort(-mean, axis=1)[:, :5]
+    top1 = (np.argmax(mean, axis=1) == label) * 1.0
+    return float(np.mean(top1) * 100), float(np.mean((top5 == label[:, None]).any(axis=1) * 1.0) * 100)

@@ -12,7 +12,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import modeling_slot, ops
 from .modeling_slot import Block, PatchEmbed, _cfg, get_sinusoid_encoding_table, register_model
 from .ops import ACT_GELU
 from .weight_cache import _WCACHE, _f32
@@ -101,6 +101,14 @@ class VisionTransformer(nn.Module):
         hv = h[:M].view(B, Nt, D)
         hv[:, 0] = cls
         hv[:, 1:] = tok.view(B, N, D)
+        if modeling_slot._INFER:
+            # one library call per block over the padded ping-pong pair (devias_encoder_block_infer: the kernels of the loop below in its order, every intermediate in the
+            # stream's workspace); the call zeroes the pad rows of its attention output itself.  Bitwise the loop's (token, logits).
+            h2 = torch.empty_like(h)
+            for blk in self.blocks:
+                blk.run_infer(h, h2, B, Nt, cdt, False)
+                h, h2 = h2, h
+            return self._cls_norm(h, M, B, Nt, D)
         scale = 64 ** -0.5
         # attention output buffer, padded like h: allocated ONCE, mhsa_fwd writes its first M rows in place every block and the pad rows
         # stay zero (no per-block zeros() + slice copy)
@@ -115,6 +123,9 @@ class VisionTransformer(nn.Module):
             u2, _, _ = ops.layernorm_fwd(h1, _f32(blk.norm2.weight), _f32(blk.norm2.bias), blk.norm2.eps)
             act = ops.gemm(u2, W1, bias=_f32(blk.mlp.fc1.bias), act=ACT_GELU)
             h = ops.gemm(act, W2, bias=_f32(blk.mlp.fc2.bias), res=h1)
+        return self._cls_norm(h, M, B, Nt, D)
+
+    def _cls_norm(self, h, M, B, Nt, D):
         tokens0 = h[:M].view(B, Nt, D)[:, 0].contiguous()                # only the cls rows need the final LayerNorm
         y, _, _ = ops.layernorm_fwd(tokens0, _f32(self.norm.weight), _f32(self.norm.bias), self.norm.eps)
         return y

@@ -28,8 +28,10 @@ import torch.nn as nn
 from . import ops
 from .functions import AggBlockFn, AggBlockFoldFn, DropMaskFn, EncoderBlockFn, HeadFn, HeadMlpFn, PatchEmbedFn
 from .regions import AggBlockRegionFn, EncoderBlockRegionFn, HeadRegionFn
+from .weight_cache import _Q_PRESCALE, _WCACHE, _f32, _use_q_prescale
 
 _REGIONS = os.environ.get("DEVIAS_REGIONS", "1") != "0"      # the fused regions (devias_amd.regions); 0 = the per-kernel Functions
+_INFER = os.environ.get("DEVIAS_INFER_REGION", "1") != "0"   # under no_grad the encoder blocks run devias_encoder_block_infer (no save arena, fc1 with one output); 0 = the training forward
 _AGG_FOLD = os.environ.get("DEVIAS_AGG_FOLD", "1") != "0"    # the folded slot attention where it applies (VisionTransformer.forward); 0 = always the unfolded form
 
 _MODEL_REGISTRY: Dict[str, callable] = {}
@@ -166,7 +168,24 @@ class Block(nn.Module):
                     ds1 = ds2 = None
             adrop = (1.0 - p_attn, source.attn_seed(index)) if p_attn > 0 else None
             return EncoderBlockFn.apply(*args, ds1, ds2, (E1, E2, adrop))
+        if _REGIONS and _INFER and ds1 is None and not torch.is_grad_enabled():
+            # nobody will ask for a backward (validation_one_epoch, final_test*, feature extraction): no arena, nothing saved; bitwise the region's output
+            x = x.contiguous()
+            return self.run_infer(x, torch.empty_like(x), B, N, cdt, _use_q_prescale(cdt))
         return (EncoderBlockRegionFn if _REGIONS else EncoderBlockFn).apply(*args, ds1, ds2)
+
+
+    def run_infer(self, x, x2, B, N, cdt, q_prescale):
+        """x [rows, D] -> x2 [rows, D], rows >= B * N, by one devias_encoder_block_infer call (ops.encoder_block_infer); q_prescale: the qkv GEMM runs on the q-scaled
+        copies of its weight and bias, as the training forward's does (the teacher keeps none)"""
+        a = self.attn
+        D = x.shape[1]
+        qkv_bias = _WCACHE.qkv_bias(a.q_bias, a.v_bias)
+        qs = (_WCACHE.get_qscaled(a.qkv.weight, D, _Q_PRESCALE, cdt), _WCACHE.get_qscaled(qkv_bias, D, _Q_PRESCALE, torch.float32)) if q_prescale else None
+        return ops.encoder_block_infer(x, x2, B, N, a.num_heads, self.norm1.eps,
+                                       (_f32(self.norm1.weight), _f32(self.norm1.bias), _f32(self.norm2.weight), _f32(self.norm2.bias)),
+                                       tuple(_WCACHE.get(w, cdt) for w in (a.qkv.weight, a.proj.weight, self.mlp.fc1.weight, self.mlp.fc2.weight)),
+                                       (qkv_bias, _f32(a.proj.bias), _f32(self.mlp.fc1.bias), _f32(self.mlp.fc2.bias)), qs)
 
 
 class PatchEmbed(nn.Module):

@@ -332,6 +332,34 @@ def wgrad_keep_stats() -> Tuple[int, int]:
     return _keep_made[0], sum(len(v) for v in _keep_free.values())
 
 
+def encoder_block_infer(x: torch.Tensor, x2: torch.Tensor, B: int, N: int, H: int, eps: float, norms, weights, biases, qscaled=None) -> torch.Tensor:
+    """devias_encoder_block_infer: one encoder block's forward with nothing kept for a backward, x [rows, D] -> x2 [rows, D] (rows >= B * N: LayerNorm and the GEMMs
+    run over all rows, the attention over (B, N) on the first B * N).  norms = fp32 (n1w, n1b, n2w, n2b); weights = (Wqkv, Wp, W1, W2) in x's dtype, nn.Linear
+    layout; biases = fp32 (q_bias | 0 | v_bias, proj, fc1, fc2); qscaled = (WqkvS, qkv_biasS) or None (devias_block_args.WqkvS).  Every intermediate lives in the
+    stream's workspace (ops.workspace): one buffer, reused by all blocks of all models on that stream."""
+    _chk(x, "encoder_block_infer.x"); _chk(x2, "encoder_block_infer.x2", x.dtype)
+    assert x.dim() == 2 and x2.shape == x.shape
+    lib = _lib.load()
+    rows, D = x.shape
+    hid = weights[2].shape[0]
+    for t in norms + biases:
+        _chk(t, "encoder_block_infer.norms / biases", torch.float32)
+    for t in weights:
+        _chk(t, "encoder_block_infer.weights", x.dtype)
+    a = _lib.BlockArgs()
+    a.B, a.N, a.D, a.H, a.hidden, a.dtype, a.eps = B, N, D, H, hid, dt_code(x.dtype), eps
+    (a.n1w, a.n1b, a.n2w, a.n2b) = [t.data_ptr() for t in norms]
+    (a.Wqkv, a.Wp, a.W1, a.W2) = [t.data_ptr() for t in weights]
+    (a.qkv_bias, a.pb, a.b1, a.b2) = [t.data_ptr() for t in biases]
+    if qscaled is not None:
+        _chk(qscaled[0], "encoder_block_infer.WqkvS", x.dtype); _chk(qscaled[1], "encoder_block_infer.qkv_biasS", torch.float32)
+        a.WqkvS, a.qkv_biasS = qscaled[0].data_ptr(), qscaled[1].data_ptr()
+    ws = workspace(lib.devias_encoder_block_infer_workspace_bytes(B, N, rows, D, H, hid, a.dtype), x.device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _lib.check(lib.devias_encoder_block_infer(ctypes.byref(a), x.data_ptr(), x2.data_ptr(), rows, _stream()), "devias_encoder_block_infer")
+    return x2
+
+
 def cast(src: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
     """out = (dtype) src, or (dtype)(scale * src) when `scale` is given (out may be src for fp32 -> fp32)."""
     _chk(src, "cast.src")

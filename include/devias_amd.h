@@ -51,6 +51,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                           a caller compiled against ABI <= 170 must zero-extend the struct (recompile),
                                     172 = devias_adamw_ema_multi, devias_ema_multi; devias_opt_tensor.reserved became the shadow pointer `ema` (same size and offsets; additive:
                                           devias_adamw_multi and devias_grad_sumsq_multi never read that word),
+                                    173 = devias_encoder_block_infer, devias_encoder_block_infer_workspace_bytes, DEVIAS_CNT_BLOCK_INFER (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -84,7 +85,8 @@ const char* devias_last_error(void);
 #define DEVIAS_CNT_SLOTM 21          /* devias_slotf_fwd / _bwd calls served by the matrix-core kernel (slotm_kernel: bf16, S in {1,2,4}, h S <= 16, D in {512,768,1024}) */
 #define DEVIAS_CNT_SLOTF_VALU 22     /* devias_slotf_fwd / _bwd calls served by the VALU kernels (slotf_fwd_kernel / slotf_bwd_kernel) */
 #define DEVIAS_CNT_SLOT 23           /* devias_slot_attn_fwd / _bwd / _kv_grad calls (the unfolded form) */
-#define DEVIAS_CNT_MAX 24
+#define DEVIAS_CNT_BLOCK_INFER 24    /* devias_encoder_block_infer calls (ABI 173): once per call, on top of the counters of the kernels it launches */
+#define DEVIAS_CNT_MAX 25
 int64_t devias_counter(int32_t id);          /* -1 for an unknown id */
 void devias_counters_reset(void);
 /* Process-wide integer options.  Each is initialised once, at first use, from its environment variable, and changed at run time by name.
@@ -629,6 +631,18 @@ int devias_encoder_block_bwd(const devias_block_args* a, const void* x, const vo
 /* ABI 171: the four weight-gradient products of a block's backward as devias_wgrad_group jobs, in the order the block runs them (dW2, dW1, dWp, dWqkv): operands from
  * dx2 (keep_g2 under ds2), the save arena and the keep_* buffers of `a`, destinations from `g` (null where not wanted: the job then has dW = NULL), beta 0 */
 int devias_encoder_block_wgrad_operands(const devias_block_args* a, const void* dx2, const devias_block_grads* g, devias_wgrad_job jobs[4]);
+/* ABI 173: the block's forward where nobody will ask for a backward (evaluation of the student under no_grad; the frozen teacher inside a training step).  The launches of
+ * devias_encoder_block_fwd in its order -- LayerNorm, qkv GEMM (on WqkvS / qkv_biasS with DEVIAS_ATTN_Q_PRESCALED when given, as there), attention, proj + residual,
+ * LayerNorm, fc1 + GELU, fc2 + residual -- and x2 bitwise its x2, with two differences: nothing is kept (a->save is not read and may be NULL; no saved pre-activation:
+ * fc1 has ONE output) and every intermediate lives in a->ws, ws_bytes >= devias_encoder_block_infer_workspace_bytes(): u (reused for u2), qkv, o, x1, hact of `rows`
+ * rows each, one pair of LayerNorm statistics, the attention's lse, and behind them the GEMMs' own workspace.  One such buffer serves all blocks of a model.
+ * rows >= B * N is the row count of x and x2 (T [rows, D]): LayerNorm and the GEMMs run over `rows`, the attention over (B, N) on the first B * N rows.  rows == B * N is
+ * the student's case; rows > B * N the teacher's (1569 tokens per clip, the token matrix padded at the END to whole 256-row tiles): the call zeroes the pad rows of o on
+ * the stream every time, so the pad rows of x2 are a function of the pad rows of x only, and no byte of the workspace is read before this call has written it.
+ * a->ds1, ds2, defer_wgrad and keep_* must be zero (training arguments) and x2 must not alias x: DEVIAS_EINVAL, like a short workspace, before anything is launched.
+ * The transposed weight copies are ignored.  Counts DEVIAS_CNT_BLOCK_INFER once per call. */
+int64_t devias_encoder_block_infer_workspace_bytes(int32_t B, int32_t N, int64_t rows, int32_t D, int32_t H, int32_t hidden, int32_t dtype);
+int devias_encoder_block_infer(const devias_block_args* a, const void* x, void* x2, int64_t rows, void* stream);
 
 /* Shared head + MaskPredictor (modeling_slot.py:392-393, 194-216): Z = slots Wh^T + bh [R,C]; Mk = sigmoid(W4 relu(W2 relu(W0 slots))) [R,G].
  * R = B*S rows, h1 / h2 = the MaskPredictor's hidden widths (512, 256). */
