@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 import torch  # noqa: F401  (must precede CDLL: see module docstring)
 
@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 173                # devias_version() of the library these prototypes describe
+ABI_VERSION = 174                # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -101,7 +101,7 @@ class AggGrads(Structure):           # devias_agg_grads
 
 
 # name -> (restype, argtypes); mirrors include/devias_amd.h one to one
-_P, _I, _L, _F = c_void_p, c_int32, c_int64, c_float
+_P, _I, _L, _F, _D = c_void_p, c_int32, c_int64, c_float, c_double
 PROTOTYPES = {
     "devias_version": (c_int, []),
     "devias_last_error": (c_char_p, []),
@@ -161,11 +161,11 @@ PROTOTYPES = {
     "devias_head_match_loss_workspace_bytes": (c_int64, [_I]),
     "devias_head_match_loss_labels_fwd": (c_int, [POINTER(LossDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "devias_head_match_loss_labels_bwd": (c_int, [POINTER(LossDims), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "devias_adamw_step": (c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P]),
+    "devias_adamw_step": (c_int, [_P, _P, _P, _P, _L, _F, _D, _D, _F, _F, _I, _F, _P]),
     "devias_grad_sumsq_multi": (c_int, [_P, _P, _P, _I, _P, _P]),
     "devias_clip_coef": (c_int, [_P, _I, _F, _P, _P]),
-    "devias_adamw_multi": (c_int, [_P, _P, _P, _I, _F, _F, _F, _F, _P, _P]),
-    "devias_adamw_ema_multi": (c_int, [_P, _P, _P, _I, _F, _F, _F, _F, _P, _F, _F, _P]),
+    "devias_adamw_multi": (c_int, [_P, _P, _P, _I, _D, _D, _F, _F, _P, _P]),
+    "devias_adamw_ema_multi": (c_int, [_P, _P, _P, _I, _D, _D, _F, _F, _P, _F, _F, _P]),
     "devias_ema_multi": (c_int, [_P, _P, _P, _I, _F, _F, _P]),
     "devias_fame_diff_color": (c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "devias_fame_blur": (c_int, [_P, _P, _I, _I, _I, _I, _F, _P]),

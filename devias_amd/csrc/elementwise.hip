@@ -192,13 +192,13 @@ __global__ void row_scale_kernel(const T* __restrict__ x, const float* __restric
 
 // ---- AdamW ------------------------------------------------------------------------------------------
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                             float* __restrict__ v, int64_t n, float lr, float b2, float c1, float c2, float eps, float wd,
                              float bc1, float bc2_sqrt, float gscale) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float gi = g[i] * gscale;
         float pi = p[i] * (1.0f - lr * wd);                      // decoupled weight decay (torch.optim.AdamW)
-        float mi = m[i] + (1.0f - b1) * (gi - m[i]);             // exp_avg.lerp_(grad, 1-beta1)
-        float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        float mi = m[i] + c1 * (gi - m[i]);                      // exp_avg.lerp_(grad, 1-beta1): c1, c2 = (float)(1.0 - beta) from the host
+        float vi = b2 * v[i] + c2 * gi * gi;
         float denom = sqrtf(vi) / bc2_sqrt + eps;
         p[i] = pi - (lr / bc1) * (mi / denom);
         m[i] = mi; v[i] = vi;
@@ -260,11 +260,13 @@ __device__ __forceinline__ float ema_lerp(float e, float w, float d, float o) {
     return a + b;
 }
 
+// b2 = (float)beta2, c1 = (float)(1.0 - beta1), c2 = (float)(1.0 - beta2): the complements come from the host in double, rounded once, as torch forms `1 - beta`
+// (1.0f - fl32(0.999) is 216 fp32 roundings off 0.001; the header's AdamW note).
 // EMA = false is devias_adamw_multi as it always was (the descriptor's last word is not read); EMA = true also streams the shadow weights of every descriptor that has
 // some, from the updated parameter still in registers: +8 bytes per parameter instead of the 12 of a pass of its own.
 template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const devias_opt_tensor* __restrict__ table, const int32_t* __restrict__ ct,
-                                                          const int32_t* __restrict__ ci, float b1, float b2, float eps, float gscale,
+                                                          const int32_t* __restrict__ ci, float b2, float c1, float c2, float eps, float gscale,
                                                           const float* __restrict__ gscale_dev, float ema_d, float ema_o) {
     const devias_opt_tensor t = table[ct[blockIdx.x]];
     const int64_t lo = (int64_t)ci[blockIdx.x] * DEVIAS_OPT_CHUNK;
@@ -276,8 +278,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const devias_opt_tenso
     auto upd = [&](float& pi, float gi, float& mi, float& vi) {
         gi *= gscale;
         pi *= decay;                                              // decoupled weight decay (torch.optim.AdamW)
-        mi = mi + (1.0f - b1) * (gi - mi);                        // exp_avg.lerp_(grad, 1-beta1)
-        vi = b2 * vi + (1.0f - b2) * gi * gi;
+        mi = mi + c1 * (gi - mi);                                 // exp_avg.lerp_(grad, 1-beta1)
+        vi = b2 * vi + c2 * gi * gi;
         pi = pi - step * (mi / (sqrtf(vi) * ib2 + eps));
     };
     const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
@@ -554,15 +556,15 @@ extern "C" int devias_act_bwd(const void* dy, const void* y, void* dx, int32_t a
 }
 
 extern "C" int devias_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                                 float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                                 double beta1, double beta2, float eps, float weight_decay, int32_t step, float grad_scale,
                                  void* stream) {
     hipStream_t st = (hipStream_t)stream;
     DEVIAS_REQUIRE(param && grad && exp_avg && exp_avg_sq && step >= 1, "devias_adamw_step: bad args");
     if (n == 0) return DEVIAS_OK;
-    float bc1 = 1.0f - powf(beta1, (float)step);
-    float bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                       beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale);
+    // the bias corrections in double, rounded once: what FusedAdamW writes into the table of devias_adamw_multi, so that the two paths see the same constants
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n, lr, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
     DEVIAS_CHECK_LAUNCH("devias_adamw_step");
     return DEVIAS_OK;
 }
@@ -584,12 +586,12 @@ extern "C" int devias_clip_coef(const float* partials, int32_t n_chunks, float m
 }
 
 extern "C" int devias_adamw_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
-                                  int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
+                                  int32_t n_chunks, double beta1, double beta2, float eps, float grad_scale,
                                   const float* grad_scale_dev, void* stream) {
     DEVIAS_REQUIRE(table && chunk_tensor && chunk_index && n_chunks >= 0, "devias_adamw_multi: bad args");
     if (n_chunks == 0) return DEVIAS_OK;
-    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, beta1, beta2,
-                       eps, grad_scale, grad_scale_dev, 0.f, 0.f);
+    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), eps, grad_scale, grad_scale_dev, 0.f, 0.f);
     DEVIAS_CHECK_LAUNCH("devias_adamw_multi");
     return DEVIAS_OK;
 }
@@ -598,14 +600,14 @@ extern "C" int devias_adamw_multi(const devias_opt_tensor* table, const int32_t*
 static inline bool ema_factors_ok(float d, float o) { return d >= 0.f && d <= 1.f && o >= 0.f && o <= 1.f; }
 
 extern "C" int devias_adamw_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
-                                      int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
+                                      int32_t n_chunks, double beta1, double beta2, float eps, float grad_scale,
                                       const float* grad_scale_dev, float ema_decay, float ema_one_minus_decay, void* stream) {
     DEVIAS_REQUIRE(n_chunks >= 0 && (n_chunks == 0 || (table && chunk_tensor && chunk_index)), "devias_adamw_ema_multi: bad args");
     DEVIAS_REQUIRE(ema_factors_ok(ema_decay, ema_one_minus_decay), "devias_adamw_ema_multi: decay %g / 1 - decay %g outside [0, 1]", (double)ema_decay,
                    (double)ema_one_minus_decay);
     if (n_chunks == 0) return DEVIAS_OK;
-    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, beta1, beta2,
-                       eps, grad_scale, grad_scale_dev, ema_decay, ema_one_minus_decay);
+    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), eps, grad_scale, grad_scale_dev, ema_decay, ema_one_minus_decay);
     DEVIAS_CHECK_LAUNCH("devias_adamw_ema_multi");
     return DEVIAS_OK;
 }

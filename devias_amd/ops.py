@@ -754,6 +754,8 @@ def head_match_loss_labels_bwd(slots_head, slots, maskp, attn, target, scene_tar
 
 
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+    """devias_adamw_step.  beta1 / beta2 cross the C ABI as doubles (here and in adamw_multi / adamw_ema_multi): the library forms `1 - beta` in double and rounds
+    once, as torch does and as ema_factors does for the EMA decay; 1.0f - fl32(0.999) would be 1.3e-5 off 0.001."""
     for t, n in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _chk(t, "adamw_step." + n, torch.float32)
     _lib.check(_lib.load().devias_adamw_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.numel(),

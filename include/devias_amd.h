@@ -52,6 +52,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     172 = devias_adamw_ema_multi, devias_ema_multi; devias_opt_tensor.reserved became the shadow pointer `ema` (same size and offsets; additive:
                                           devias_adamw_multi and devias_grad_sumsq_multi never read that word),
                                     173 = devias_encoder_block_infer, devias_encoder_block_infer_workspace_bytes, DEVIAS_CNT_BLOCK_INFER (additive),
+                                    174 = devias_adamw_step, devias_adamw_multi, devias_adamw_ema_multi take beta1 / beta2 as double (recompile callers),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -485,9 +486,13 @@ int devias_head_match_loss_labels_bwd(const devias_loss_dims* d, const void* slo
 /* ---------------------------------------------------------------------------------------------------
  * Fused AdamW over a flat fp32 parameter range (torch.optim.AdamW semantics, utils/optim_factory.py:132-133;
  * decoupled weight decay, bias correction by step).  grad_scale multiplies the gradient first (1/world, loss scale).
+ * beta1 / beta2 are doubles (ABI 174), in all three AdamW entry points: the kernels' constants are (float)beta2, (float)(1.0 - beta1) and
+ * (float)(1.0 - beta2), formed by the host side in double and rounded once, NOT 1.0f - (float)beta: torch evaluates `1 - beta` in double, and
+ * 1.0f - fl32(0.999) = 9.99987e-4 is 1.3e-5 (216 fp32 roundings) off 0.001.  devias_adamw_step forms bc1 = 1 - beta1^step and sqrt(1 - beta2^step) in
+ * double as well, the values a caller of devias_adamw_multi writes into its table: the two paths see the same hyper-parameters.
  * ------------------------------------------------------------------------------------------------- */
 int devias_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                      float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                      float lr, double beta1, double beta2, float eps, float weight_decay, int32_t step,
                       float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
@@ -501,7 +506,10 @@ int devias_adamw_step(float* param, const float* grad, float* exp_avg, float* ex
  * `chunk_index[c]` (device int32 [n_chunks]) enumerate fixed DEVIAS_OPT_CHUNK-element pieces of the tensors, one workgroup each.
  *   devias_grad_sumsq_multi: partials[c] = sum of squares of chunk c (fp32, fixed order inside the chunk)
  *   devias_clip_coef:        out[0] = sqrt(sum_c partials[c]) (fixed order), out[1] = max_norm > 0 ?
- *                            min(1, max_norm / (out[0] + 1e-6)) : 1   (clip_grad_norm_ semantics)
+ *                            min(1, max_norm / (out[0] + 1e-6)) : 1   (clip_grad_norm_ semantics).  The coefficient is EXACTLY 1.0f in three cases:
+ *                            max_norm = 0 (the norm is still written: get_grad_norm_ alone); a zero norm (all-zero gradients or n_chunks = 0) under any
+ *                            max_norm >= 1e-6; max_norm above the norm by more than 1e-6.  It is below 1 wherever max_norm < norm + 1e-6, a norm of the
+ *                            order of 1e-6 included (max_norm = 1e-6 at norm 2e-6 gives 1/3, not 1/2).
  *   devias_adamw_multi:      g' = g * grad_scale * (grad_scale_dev ? *grad_scale_dev : 1); AdamW update as devias_adamw_step
  * No host synchronisation anywhere: the clip coefficient stays on the device.
  *
@@ -533,10 +541,10 @@ int devias_grad_sumsq_multi(const devias_opt_tensor* table, const int32_t* chunk
                             int32_t n_chunks, float* partials, void* stream);
 int devias_clip_coef(const float* partials, int32_t n_chunks, float max_norm, float* out, void* stream);
 int devias_adamw_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
-                       int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
+                       int32_t n_chunks, double beta1, double beta2, float eps, float grad_scale,
                        const float* grad_scale_dev, void* stream);
 int devias_adamw_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
-                           int32_t n_chunks, float beta1, float beta2, float eps, float grad_scale,
+                           int32_t n_chunks, double beta1, double beta2, float eps, float grad_scale,
                            const float* grad_scale_dev, float ema_decay, float ema_one_minus_decay, void* stream);
 int devias_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                      int32_t n_chunks, float ema_decay, float ema_one_minus_decay, void* stream);

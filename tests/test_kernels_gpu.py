@@ -508,6 +508,10 @@ def test_head_match_loss_refuses_rows_that_disagree():
     assert o.counters() == before
 
 
+# The three optimizer tests below pin the API flow against torch.optim.AdamW over several steps: per-group lr and weight decay, a plan rebuilt when a parameter has no
+# gradient, parity of the fused norm and clip with clip_grad_norm_, the per-tensor path next to the multi-tensor one.  Their metric, rel on the PARAMETERS, cannot see an
+# error of a few per cent of the update and never looks at exp_avg: numerical accuracy (every element of p, exp_avg, exp_avg_sq, the partial sums, norm and coefficient
+# against float64 bounds) is held by tests/test_optim_bounds_gpu.py with tests/optim_bounds.py.
 def test_adamw_matches_torch():
     o = ops()
     p = rnd(10007, seed=60); g = rnd(10007, seed=61)

@@ -77,6 +77,8 @@ def main():
     if a.other_lib:
         other = ctypes.CDLL(a.other_lib)
         other.devias_adamw_multi.restype, other.devias_adamw_multi.argtypes = _lib.PROTOTYPES["devias_adamw_multi"]
+        if other.devias_version() < 174:                       # before ABI 174 the betas crossed as floats
+            other.devias_adamw_multi.argtypes = [ctypes.c_float if t is ctypes.c_double else t for t in other.devias_adamw_multi.argtypes]
 
         def adamw_other():
             rc = other.devias_adamw_multi(T[0].data_ptr(), T[1].data_ptr(), T[2].data_ptr(), T[1].numel(), betas[0], betas[1], eps, 1.0, None,
