@@ -11,7 +11,12 @@ def __getattr__(name):
     if name in ("create_model", "VisionTransformer", "slot_vit_base_patch16_224", "slot_vit_small_patch16_224",
                 "slot_vit_large_patch16_224"):
         from . import modeling_slot
+        if name == "create_model":
+            from . import modeling_slot_fusion  # noqa: F401  (registers the downstream factories: create_model("slot_fusion_vit_base_patch16_224", ...))
         return getattr(modeling_slot, name)
+    if name in ("slot_fusion_vit_base_patch16_224", "slot_fusion_vit_small_patch16_224", "slot_fusion_vit_large_patch16_224"):
+        from . import modeling_slot_fusion
+        return getattr(modeling_slot_fusion, name)
     if name == "TrainLoss":
         from .train_loss import TrainLoss
         return TrainLoss

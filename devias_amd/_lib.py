@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 174                # devias_version() of the library these prototypes describe
+ABI_VERSION = 175                # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -73,6 +73,16 @@ class HeadArgs(Structure):           # devias_head_args
 
 class HeadGrads(Structure):          # devias_head_grads
     _fields_ = [(n, c_void_p) for n in ("dWh", "dbh", "dW0", "db0", "dW2", "db2", "dW4", "db4")]
+
+
+class FusionArgs(Structure):         # devias_fusion_args (ABI 175); struct_size = ctypes.sizeof(FusionArgs)
+    _fields_ = [(n, c_int32) for n in ("struct_size", "B", "S", "D", "nb", "ns", "Cd", "dtype", "use_input_ln")] + [("eps_norm", c_float), ("eps_ln", c_float)] + \
+               [(n, c_void_p) for n in ("Wh", "Wd", "Wc", "bh", "an_w", "an_b", "sn_w", "sn_b", "bd", "ln_w", "ln_b", "in_w", "in_b", "bc", "drop_mask", "ws")] + [("ws_bytes", c_int64)]
+
+
+class FusionGrads(Structure):        # devias_fusion_grads
+    _fields_ = [("struct_size", c_int32), ("reserved", c_int32)] + \
+               [(n, c_void_p) for n in ("dan_w", "dan_b", "dsn_w", "dsn_b", "dWd", "dbd", "dln_w", "dln_b", "din_w", "din_b", "dWc", "dbc")]
 
 
 AGG_MAX_DEPTH = 16                   # DEVIAS_AGG_MAX_DEPTH
@@ -186,6 +196,14 @@ PROTOTYPES = {
     "devias_head_save_bytes": (c_int64, [_I, _I, _I, _I, _I]),
     "devias_head_fwd": (c_int, [POINTER(HeadArgs), _P, _P, _P, _P, _P]),
     "devias_head_bwd": (c_int, [POINTER(HeadArgs), _P, _P, _P, _P, _P, _P, POINTER(HeadGrads), _P]),
+    "devias_fusion_head_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I, _I]),
+    "devias_fusion_head_save_bytes": (c_int64, [_I, _I, _I]),
+    "devias_fusion_head_fwd": (c_int, [POINTER(FusionArgs), _P, _P, _P, _P, _P, _P]),
+    "devias_fusion_head_bwd": (c_int, [POINTER(FusionArgs), _P, _P, _P, _P, _P, _P, _P, POINTER(FusionGrads), _P]),
+    "devias_softmax_ce_workspace_bytes": (c_int64, [_I]),
+    "devias_softmax_ce_fwd": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "devias_softmax_ce_bwd": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "devias_region_counter": (c_int64, [c_int32]),
     "devias_agg_block_save_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_scratch_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_workspace_bytes": (c_int64, [POINTER(AggArgs)]),
@@ -203,6 +221,7 @@ COUNTERS = {"gemm128_f32": 0, "gemm128_bf16": 1, "gemm_ss": 2, "gemm256": 3, "ge
             "mhsa_fwd_bf16": 6, "mhsa_bwd_bf16": 7, "mhsa_fwd_f32": 8, "mhsa_bwd_f32": 9, "mhsa_bwd_fused": 10, "gemm_sk": 11, "gemm256w": 12, "gemm_smallm": 13, "gemm256d": 14,
             "dkdv1w": 15, "dkdv1w_pers": 16, "dkdv1w_rest": 17, "dkdv2w": 18, "mhsa_qpre": 19, "loss_labels": 20,
             "slotm": 21, "slotf_valu": 22, "slot": 23, "block_infer": 24}     # DEVIAS_CNT_*
+REGION_COUNTERS = {"fusion_head": 0, "softmax_ce": 1}     # DEVIAS_RCNT_* (devias_region_counter: the second bank, ABI 175)
 OPT_CHUNK = 16384          # DEVIAS_OPT_CHUNK
 OPT_TENSOR_BYTES = 64      # sizeof(devias_opt_tensor)
 

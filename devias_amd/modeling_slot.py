@@ -420,18 +420,24 @@ class VisionTransformer(nn.Module):
             h = blk.run(h, B, N, cdt, i, src)
         return h          # [B*N, D], BEFORE the final LayerNorm (it is fused into AggBlockFn)
 
+    def _aggregate(self, h, B):
+        """final LayerNorm + aggregation block on the encoder's output h [B*N, D] -> (slots [B*S, D], the last layer's slot softmax); shared with the downstream model"""
+        N, D, cdt = self.patch_embed.num_patches, self.embed_dim, self.compute_dtype
+        ab = self.agg_block
+        S = ab.num_latents
+        meta = (B, N, S, ab.depth, ab.weight_tie_layers, ab.heads, ab.dim_head, self.norm.eps, ab.last_layer[0].eps, cdt)
+        fold = _AGG_FOLD and S <= 4 and D in (384, 512, 768, 1024)
+        return ((AggBlockRegionFn if _REGIONS else AggBlockFoldFn) if fold else AggBlockFn).apply(h, self.norm.weight, self.norm.bias, ab.latents, ab.last_layer[0].weight,
+                                                                                                ab.last_layer[0].bias, meta, *ab.layer_params())
+
     def forward(self, x, return_attn=False):
         B = x.shape[0]
         N = self.patch_embed.num_patches
         D = self.embed_dim
         cdt = self.compute_dtype
         h = self.forward_features(x, return_attn)
-        ab = self.agg_block
-        S = ab.num_latents
-        meta = (B, N, S, ab.depth, ab.weight_tie_layers, ab.heads, ab.dim_head, self.norm.eps, ab.last_layer[0].eps, cdt)
-        fold = _AGG_FOLD and S <= 4 and D in (384, 512, 768, 1024)
-        slots, attn = ((AggBlockRegionFn if _REGIONS else AggBlockFoldFn) if fold else AggBlockFn).apply(h, self.norm.weight, self.norm.bias, ab.latents, ab.last_layer[0].weight,
-                                                                      ab.last_layer[0].bias, meta, *ab.layer_params())
+        S = self.agg_block.num_latents
+        slots, attn = self._aggregate(h, B)
         if self.slot_matching_method == 'hard_select':
             raise NotImplementedError("only slot_matching_method='matching' is on the DEVIAS training path "
                                       "(the reference's hard_select branch returns empty lists, modeling_slot.py:388)")

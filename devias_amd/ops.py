@@ -107,6 +107,12 @@ def counters(reset: bool = False) -> dict:
     return out
 
 
+def region_counters() -> dict:
+    """calls per fused region / loss entry point of the second counter bank (devias_region_counter) since the last reset; counters(reset=True) resets both banks"""
+    lib = _lib.load()
+    return {k: int(lib.devias_region_counter(i)) for k, i in _lib.REGION_COUNTERS.items()}
+
+
 def auto_split_k(M: int, N: int, K: int, bk: int = 64) -> int:
     """Split the long reduction of a weight-gradient GEMM so that (tiles x splits) is just under ONE full round of the kernel that will run it:
     2 slots per CU for the bf16 256x256 kernel counted in 256x128 halves (512 on MI355X), 3 per CU for the 128x128 kernel (768); the CU count
@@ -811,3 +817,32 @@ def ema_multi(table, chunk_tensor, chunk_index, ema_decay):
     d, o = ema_factors(ema_decay)
     _lib.check(_lib.load().devias_ema_multi(table.data_ptr(), chunk_tensor.data_ptr(), chunk_index.data_ptr(), chunk_tensor.numel(), d, o, _stream()),
                "devias_ema_multi")
+
+
+def _chk_ce(who, logits, target):
+    _chk(logits, who + ".logits")
+    _chk(target, who + ".target", torch.int64)
+    if logits.dim() != 2 or target.shape != (logits.shape[0],) or logits.shape[0] == 0:
+        raise ValueError(f"{who}: logits [B, C] and target [B] expected, got {tuple(logits.shape)} and {tuple(target.shape)}")
+    return logits.shape
+
+
+def softmax_ce_fwd(logits: torch.Tensor, target: torch.Tensor, smoothing: float = 0.0) -> torch.Tensor:
+    """devias_softmax_ce_fwd: label-smoothing cross-entropy of logits [B, C] (fp32 or bf16) against int64 targets [B] -> fp32 loss [1]"""
+    B, C = _chk_ce("softmax_ce_fwd", logits, target)
+    lib = _lib.load()
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    ws = workspace(lib.devias_softmax_ce_workspace_bytes(B), logits.device)
+    _lib.check(lib.devias_softmax_ce_fwd(logits.data_ptr(), target.data_ptr(), B, C, dt_code(logits.dtype), float(smoothing), loss.data_ptr(), ws.data_ptr(), _stream()),
+               "devias_softmax_ce_fwd")
+    return loss
+
+
+def softmax_ce_bwd(logits: torch.Tensor, target: torch.Tensor, g_loss: torch.Tensor, smoothing: float = 0.0) -> torch.Tensor:
+    """devias_softmax_ce_bwd: g_loss is the fp32 DEVICE scalar arriving on the loss"""
+    B, C = _chk_ce("softmax_ce_bwd", logits, target)
+    _chk(g_loss, "softmax_ce_bwd.g_loss", torch.float32)
+    dz = torch.empty_like(logits)
+    _lib.check(_lib.load().devias_softmax_ce_bwd(logits.data_ptr(), target.data_ptr(), B, C, dt_code(logits.dtype), float(smoothing), g_loss.data_ptr(), dz.data_ptr(), _stream()),
+               "devias_softmax_ce_bwd")
+    return dz

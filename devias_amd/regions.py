@@ -220,6 +220,83 @@ class HeadRegionFn(Function):
         return (dslots, *gd.out, None, None)
 
 
+class FusionHeadFn(Function):
+    """Everything after the slots of the slot-fusion classifier (model/modeling_slot_fusion.py:379-400, MLPHead :42-53) as one devias_fusion_head_fwd / _bwd call:
+    slots [B*S, D] -> (input [B, 2D], out [B, Cd], idx int32 [B, 2]).  The pre-trained head (hw, hb) only selects and gets no gradient; drop_mask: optional fp32
+    [B, D] of 0 / (1 / keep), fc_dropout on relu(h).  meta's last entry is the caller's torch.is_grad_enabled(), read BEFORE apply (inside forward autograd is
+    always off, and needs_input_grad reports requires_grad whatever the mode): where it is False, or no input requires a gradient, nothing is saved -- no arena, and
+    the library keeps u, r and the statistics in its workspace (devias_fusion_head_fwd with save = NULL; same bits)."""
+
+    @staticmethod
+    def forward(ctx, slots, hw, hb, an_w, an_b, sn_w, sn_b, dw, db, lw, lb, iw, ib, cw, cb, meta, drop_mask=None):
+        B, S, nb, eps_norm, eps_ln, cdt, grad_enabled = meta
+        lib = _L.load()
+        dev = slots.device
+        slots = slots.contiguous()
+        R, D = slots.shape
+        Cd, C = cw.shape[0], hw.shape[0]
+        assert R == B * S and dw.shape == (D // 2, D) and cw.shape[1] == D and hw.shape[1] == D
+        dt = ops.dt_code(cdt)
+        mats = [_WCACHE.get(w, cdt) for w in (hw, dw, cw)]
+        vecs = [_f32(t) for t in (hb, an_w, an_b, sn_w, sn_b, db, lw, lb)] + [(_f32(t) if t is not None else None) for t in (iw, ib)] + [_f32(cb)]
+        a = _L.FusionArgs()
+        a.struct_size = _ct.sizeof(_L.FusionArgs)
+        a.B, a.S, a.D, a.nb, a.ns, a.Cd, a.dtype, a.use_input_ln = B, S, D, nb, C - nb, Cd, dt, int(iw is not None)
+        a.eps_norm, a.eps_ln = eps_norm, eps_ln
+        (a.Wh, a.Wd, a.Wc) = [t.data_ptr() for t in mats]
+        (a.bh, a.an_w, a.an_b, a.sn_w, a.sn_b, a.bd, a.ln_w, a.ln_b, a.in_w, a.in_b, a.bc) = [(t.data_ptr() if t is not None else None) for t in vecs]
+        if drop_mask is not None:
+            drop_mask = ops._chk(drop_mask, "fusion_head.drop_mask", torch.float32)
+            assert drop_mask.shape == (B, D)
+            a.drop_mask = drop_mask.data_ptr()
+        nws = lib.devias_fusion_head_workspace_bytes(B, S, D, C, Cd, dt)
+        if nws <= 0:
+            raise NotImplementedError(f"devias_fusion_head: unsupported dims B={B} S={S} D={D} C={C} Cd={Cd} (D in 384 / 768 / 1024, S <= 4, Cd >= 2)")
+        ws = ops.workspace(nws, dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        need_bwd = bool(grad_enabled) and any(ctx.needs_input_grad)
+        save = torch.empty((lib.devias_fusion_head_save_bytes(B, D, dt),), dtype=torch.uint8, device=dev) if need_bwd else None
+        inp = torch.empty((B, 2 * D), dtype=cdt, device=dev)
+        out = torch.empty((B, Cd), dtype=cdt, device=dev)
+        idx = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        _L.check(lib.devias_fusion_head_fwd(_ct.byref(a), slots.data_ptr(), inp.data_ptr(), out.data_ptr(), idx.data_ptr(), save.data_ptr() if save is not None else None,
+                                            ops._stream()), "devias_fusion_head_fwd")
+        ctx.mark_non_differentiable(idx)
+        if need_bwd:
+            ctx.args = a
+            ctx.keep = (mats + vecs, save, slots, inp, idx, drop_mask)
+            ctx.x_version = slots._version
+            ctx.params = (an_w, an_b, sn_w, sn_b, dw, db, lw, lb, iw, ib, cw, cb)
+        else:
+            ctx.keep = ctx.args = None
+        return inp, out, idx
+
+    @staticmethod
+    def backward(ctx, dinp, dout, _didx):
+        lib = _L.load()
+        _region_state(ctx, "FusionHeadFn", ctx.keep[2] if ctx.keep is not None else None)
+        a = ctx.args
+        keep, save, slots, inp, idx, drop_mask = ctx.keep
+        an_w, an_b, sn_w, sn_b, dw, db, lw, lb, iw, ib, cw, cb = ctx.params
+        dev = slots.device
+        dout = dout.contiguous() if dout is not None else torch.zeros((a.B, a.Cd), dtype=slots.dtype, device=dev)
+        dinp = dinp.contiguous() if dinp is not None else None
+        live = [p for p in (an_w, an_b, sn_w, sn_b, dw, db, lw, lb, iw, ib, cw, cb)]
+        gd = _GradDest([(p, tuple(p.shape)) for p in live if p is not None], dev)
+        it = iter(gd.out)
+        outs = [(next(it) if p is not None else None) for p in live]
+        g = _L.FusionGrads()
+        g.struct_size = _ct.sizeof(_L.FusionGrads)
+        (g.dan_w, g.dan_b, g.dsn_w, g.dsn_b, g.dWd, g.dbd, g.dln_w, g.dln_b, g.din_w, g.din_b, g.dWc, g.dbc) = [(t.data_ptr() if t is not None else None) for t in outs]
+        ws = ops.workspace(a.ws_bytes, dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        dslots = torch.empty_like(slots)
+        _L.check(lib.devias_fusion_head_bwd(_ct.byref(a), slots.data_ptr(), idx.data_ptr(), inp.data_ptr(), save.data_ptr(), dout.data_ptr(),
+                                            dinp.data_ptr() if dinp is not None else None, dslots.data_ptr(), _ct.byref(g), ops._stream()), "devias_fusion_head_bwd")
+        ctx.keep = ctx.args = None
+        return (dslots, None, None, *outs, None, None)
+
+
 _AGG_MATS = ("to_q", "to_k", "to_v", "to_out_w", "ff0_w", "ff3_w")                       # -> devias_agg_layer_params.Wq Wk Wv Wo W1 W2
 _AGG_VECS = ("to_out_b", "norm_w", "norm_b", "ctx_w", "ctx_b", "ff0_b", "ff3_b", "ffn_w", "ffn_b")   # -> bo norm_w norm_b ctx_w ctx_b b1 b2 ffn_w ffn_b
 # (devias_agg_layer_grads -- dWq dWk dWv dWo dbo dnorm_w dnorm_b dctx_w dctx_b dW1 db1 dW2 db2 dffn_w dffn_b -- is in _LAYER_KEYS order)

@@ -53,6 +53,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                           devias_adamw_multi and devias_grad_sumsq_multi never read that word),
                                     173 = devias_encoder_block_infer, devias_encoder_block_infer_workspace_bytes, DEVIAS_CNT_BLOCK_INFER (additive),
                                     174 = devias_adamw_step, devias_adamw_multi, devias_adamw_ema_multi take beta1 / beta2 as double (recompile callers),
+                                    175 = devias_fusion_head_* (the slot-fusion classifier's head region), devias_softmax_ce_*, devias_region_counter (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -88,6 +89,11 @@ const char* devias_last_error(void);
 #define DEVIAS_CNT_SLOT 23           /* devias_slot_attn_fwd / _bwd / _kv_grad calls (the unfolded form) */
 #define DEVIAS_CNT_BLOCK_INFER 24    /* devias_encoder_block_infer calls (ABI 173): once per call, on top of the counters of the kernels it launches */
 #define DEVIAS_CNT_MAX 25
+/* ABI 175: a second bank, one counter per fused region / loss entry point added since (the bank above is closed at 25 ids: callers test devias_counter(25) == -1).
+ * devias_region_counter(id): calls that passed validation and launched, since the last devias_counters_reset(); -1 for an unknown id. */
+#define DEVIAS_RCNT_FUSION_HEAD 0    /* devias_fusion_head_fwd / _bwd: 1 per call */
+#define DEVIAS_RCNT_SOFTMAX_CE 1     /* devias_softmax_ce_fwd / _bwd: 1 per call */
+#define DEVIAS_RCNT_MAX 2
 int64_t devias_counter(int32_t id);          /* -1 for an unknown id */
 void devias_counters_reset(void);
 /* Process-wide integer options.  Each is initialised once, at first use, from its environment variable, and changed at run time by name.
@@ -668,6 +674,58 @@ int64_t devias_head_save_bytes(int32_t R, int32_t D, int32_t h1, int32_t h2, int
 int devias_head_fwd(const devias_head_args* a, const void* slots, void* Z, void* Mk, void* save, void* stream);
 int devias_head_bwd(const devias_head_args* a, const void* slots, const void* Mk, const void* save, const void* dZ, const void* dM, void* dslots,
                     const devias_head_grads* g, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 175: downstream fine-tuning (docs/DOWNSTREAM.md).  Everything after the slots of the slot-fusion classifier (model/modeling_slot_fusion.py:23-53, 364-403;
+ * head form 'mlp' + 'concat'), one call per direction:
+ *   Z = slots Wh^T + bh [B*S, nb+ns] (the frozen pre-trained head; NOT differentiated, no fc-dropout on its input)
+ *   idx[b] = (argmax_s max_{c<nb} softmax(Z)[b,s,c], argmax_s max_{c>=nb} ...), first slot wins ties (devias_slot_select); always in [0, S)
+ *   input[b] = [LN(X[b, idx[b,0]]; action_norm) | LN(X[b, idx[b,1]]; scene_norm)], eps_norm                         T [B, 2D]
+ *   u[b]     = [Wd input[b,:D] + bd | Wd input[b,D:] + bd]   (BOTH tokens through fc_action_down, :43-44)             T [B, D], saved
+ *   h[b]     = [LN(u[b,:D/2]) | LN(u[b,D/2:])] with fc_action_ln, eps_ln; if use_input_ln: h = LN(h; fc_input_ln), eps_ln
+ *   r[b]     = relu(h[b]) * drop_mask[b]                                                                             T [B, D], saved
+ *   out      = r Wc^T + bc                                                                                           T [B, Cd]
+ * Every statistic is fp32 (two-pass); nothing between u and r is rounded to T.  Backward: dslots[b,s] = [s = idx[b,0]] g_a + [s = idx[b,1]] g_s, EVERY row written
+ * (zero for an unselected slot, the fp32 sum rounded once where both picks are one slot); the ReLU mask is the saved r > 0.  The parameter gradients of the four
+ * LayerNorms are per-clip partial sums reduced over the clips in index order: bitwise equal run to run, no atomics.  Wh / bh and the model's fc_scene_down /
+ * fc_scene_ln get no gradient (the latter two are never read).
+ * Both structs start with struct_size = sizeof(the struct): a mismatch is DEVIAS_EINVAL (a caller compiled against another layout), like a null pointer, a bad dtype
+ * or a short workspace -- all before anything is launched.  Supported: D in {384, 768, 1024}, 1 <= S <= 4, Cd >= 2, B >= 1, nb >= 1, ns >= 1; anything else is
+ * DEVIAS_EUNSUPPORTED (the size queries then return 0).  Each call counts DEVIAS_RCNT_FUSION_HEAD once.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t struct_size;                 /* sizeof(devias_fusion_args) */
+    int32_t B, S, D, nb, ns, Cd, dtype, use_input_ln;
+    float eps_norm, eps_ln;              /* action_norm / scene_norm (the model's norm_layer: 1e-6); fc_action_ln / fc_input_ln (nn.LayerNorm: 1e-5) */
+    const void *Wh, *Wd, *Wc;            /* T: head [nb+ns, D], fc_action_down [D/2, D], classifier [Cd, D] */
+    const float *bh, *an_w, *an_b, *sn_w, *sn_b, *bd, *ln_w, *ln_b, *in_w, *in_b, *bc;   /* in_w / in_b: fc_input_ln, may be NULL without use_input_ln */
+    const float* drop_mask;              /* optional fp32 [B, D], 0 or 1/keep: fc_dropout on relu(h) */
+    float* ws; int64_t ws_bytes;         /* devias_fusion_head_workspace_bytes() */
+} devias_fusion_args;
+typedef struct {
+    int32_t struct_size;                 /* sizeof(devias_fusion_grads) */
+    int32_t reserved;
+    float *dan_w, *dan_b, *dsn_w, *dsn_b, *dWd, *dbd, *dln_w, *dln_b, *din_w, *din_b, *dWc, *dbc;      /* fp32, written (not accumulated) */
+} devias_fusion_grads;
+int64_t devias_fusion_head_workspace_bytes(int32_t B, int32_t S, int32_t D, int32_t C, int32_t Cd, int32_t dtype);      /* C = nb + ns */
+int64_t devias_fusion_head_save_bytes(int32_t B, int32_t D, int32_t dtype);
+/* slots T [B*S, D] -> input T [B, 2D], out T [B, Cd], idx int32 [B, 2].  save: devias_fusion_head_save_bytes() bytes for the backward, or NULL where nobody will ask
+ * for one (u, r and the statistics then live in the workspace; same bits).  Layout of save, each piece rounded up to 256 bytes: u T [B, D]; r T [B, D]; fp32 [2B, 2]
+ * (mean, rstd) of the two norms; fp32 [B, 6] (mean, rstd) of the two half rows and of fc_input_ln. */
+int devias_fusion_head_fwd(const devias_fusion_args* a, const void* slots, void* input, void* out, int32_t* idx, void* save, void* stream);
+/* dout T [B, Cd]; dinput: optional T [B, 2D], the gradient arriving on the returned `input`; dslots T [B*S, D].  idx must be the forward's (a value outside [0, S)
+ * is clamped into it in both directions, so it is never an address outside the clip and every partial sum is written). */
+int devias_fusion_head_bwd(const devias_fusion_args* a, const void* slots, const int32_t* idx, const void* input, const void* save, const void* dout, const void* dinput,
+                           void* dslots, const devias_fusion_grads* g, void* stream);
+/* timm's LabelSmoothingCrossEntropy(smoothing): loss = mean_b[(1 - e)(lse_b - z[b,y_b]) + e (lse_b - mean_c z[b,c])], e = 0: plain cross-entropy.  logits T [B, C]
+ * (fp32 or bf16), target int64 [B], statistics fp32, one workgroup per row, loss an fp32 device scalar; ws: devias_softmax_ce_workspace_bytes(B).
+ * backward: dlogits = g / B (softmax(z) - (1 - e) onehot(y) - e / C) with g read from the DEVICE scalar g_loss (no host sync for loss / update_freq).
+ * Labels are data: a target outside [0, C) is never used as an index; that row's loss is NaN (so the mean is) and its gradient row is zero.
+ * B >= 1, C >= 2, 0 <= smoothing < 1, else DEVIAS_EINVAL before any launch.  Each call counts DEVIAS_RCNT_SOFTMAX_CE once. */
+int64_t devias_softmax_ce_workspace_bytes(int32_t B);
+int devias_softmax_ce_fwd(const void* logits, const int64_t* target, int32_t B, int32_t C, int32_t dtype, float smoothing, float* loss, float* ws, void* stream);
+int devias_softmax_ce_bwd(const void* logits, const int64_t* target, int32_t B, int32_t C, int32_t dtype, float smoothing, const float* g_loss, void* dlogits, void* stream);
+int64_t devias_region_counter(int32_t id);      /* DEVIAS_RCNT_* */
 
 /* Final LayerNorm + AggregationBlock with the folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:105-139;
  * agg_block/attention.py:29-40,66-72,108-141): `depth` layers over `tied ? 1 : depth` weight sets; S <= 4 slots. */
