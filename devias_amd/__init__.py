@@ -13,6 +13,7 @@ def __getattr__(name):
         from . import modeling_slot
         if name == "create_model":
             from . import modeling_slot_fusion  # noqa: F401  (registers the downstream factories: create_model("slot_fusion_vit_base_patch16_224", ...))
+            from . import modeling_finetune  # noqa: F401  (registers the plain video ViT: create_model("vit_base_patch16_224", use_mean_pooling=..., ...))
         return getattr(modeling_slot, name)
     if name in ("slot_fusion_vit_base_patch16_224", "slot_fusion_vit_small_patch16_224", "slot_fusion_vit_large_patch16_224"):
         from . import modeling_slot_fusion

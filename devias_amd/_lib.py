@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 175                # devias_version() of the library these prototypes describe
+ABI_VERSION = 176               # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -85,6 +85,17 @@ class FusionGrads(Structure):        # devias_fusion_grads
                [(n, c_void_p) for n in ("dan_w", "dan_b", "dsn_w", "dsn_b", "dWd", "dbd", "dln_w", "dln_b", "din_w", "din_b", "dWc", "dbc")]
 
 
+class PoolHeadArgs(Structure):       # devias_pool_head_args (ABI 176); struct_size = ctypes.sizeof(PoolHeadArgs)
+    _fields_ = [(n, c_int32) for n in ("struct_size", "B", "Nt", "D", "C", "dtype", "pool")] + [("eps", c_float)] + \
+               [(n, c_void_p) for n in ("W", "bias", "ln_w", "ln_b", "drop_mask", "ws")] + [("ws_bytes", c_int64)]
+
+
+class PoolHeadGrads(Structure):      # devias_pool_head_grads
+    _fields_ = [("struct_size", c_int32), ("reserved", c_int32)] + [(n, c_void_p) for n in ("dW", "db", "dln_w", "dln_b")]
+
+
+POOL_MEAN, POOL_CLS = 0, 1           # DEVIAS_POOL_MEAN / DEVIAS_POOL_CLS
+POOL_HEAD_CHUNK = 64                 # DEVIAS_POOL_HEAD_CHUNK: token rows one workgroup of the region's streaming kernels covers
 AGG_MAX_DEPTH = 16                   # DEVIAS_AGG_MAX_DEPTH
 AGG_PARAM_FIELDS = ("Wq", "Wk", "Wv", "Wo", "W1", "W2", "bo", "norm_w", "norm_b", "ctx_w", "ctx_b", "b1", "b2", "ffn_w", "ffn_b")
 AGG_GRAD_FIELDS = ("dWq", "dWk", "dWv", "dWo", "dbo", "dnorm_w", "dnorm_b", "dctx_w", "dctx_b", "dW1", "db1", "dW2", "db2", "dffn_w", "dffn_b")
@@ -204,6 +215,11 @@ PROTOTYPES = {
     "devias_softmax_ce_fwd": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "devias_softmax_ce_bwd": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "devias_region_counter": (c_int64, [c_int32]),
+    "devias_pool_head_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I]),
+    "devias_pool_head_save_bytes": (c_int64, [_I, _I, _I]),
+    "devias_pool_head_fwd": (c_int, [POINTER(PoolHeadArgs), _P, _P, _P, _P, _P]),
+    "devias_pool_head_bwd": (c_int, [POINTER(PoolHeadArgs), _P, _P, _P, _P, POINTER(PoolHeadGrads), _P]),
+    "devias_pool_head_launches": (c_int64, []),
     "devias_agg_block_save_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_scratch_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_workspace_bytes": (c_int64, [POINTER(AggArgs)]),

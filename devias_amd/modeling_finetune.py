@@ -1,10 +1,15 @@
-"""Frozen scene teacher (model/modeling_finetune.py:178-334 of the reference, `vit_base_patch16_224` with
-use_mean_pooling=False): cls token + N patch tokens, forward only, on the same HIP kernels as the student.
+"""The plain video ViT (model/modeling_finetune.py:178-334 of the reference, `vit_base_patch16_224`): the scene teacher behind --scene_model_path
+(use_mean_pooling=False: cls token + N patch tokens) and the action baseline (use_mean_pooling=True, the reference's default: fc_norm of the mean token).
 
-`forward(x, return_attn=False)` returns `(token[B, D], logits[B, num_classes])` like the reference (:314-325); it is what
-`engine/engine_for_slot.train_class_batch` calls under `torch.no_grad()` (:52-53).  N + 1 = 1569 tokens per clip is odd, so the
-token matrix is padded (once, with zero rows at the END of the batch) to a multiple of 256 rows to stay on the full-tile GEMM
-kernels; the attention kernels handle the ragged sequence length themselves."""
+`forward(x, return_attn=False)` returns `(token[B, D], logits[B, num_classes])` like the reference (:314-325).
+
+Frozen (eval(), or under torch.no_grad(): what `engine/engine_for_slot.train_class_batch` calls, :52-53): forward only, nothing saved.  In cls-token mode
+N + 1 = 1569 tokens per clip is odd, so the token matrix is padded (once, with zero rows at the END of the batch) to a multiple of 256 rows to stay on the
+full-tile GEMM kernels; the attention kernels handle the ragged sequence length themselves.  Mean-pooling mode runs the blocks' forward-only region on the
+unpadded tokens and the pooled-head region without a save arena.
+
+Trainable (`self.training and torch.is_grad_enabled()`): PatchEmbedFn, the cls row prepended in cls-token mode, Block.run per block (the slot model's training
+path, unpadded: B * 1569 rows run the 128 x 128 GEMM kernels) and regions.PoolHeadRegionFn (csrc/pool_head.hip) for everything after the encoder."""
 from __future__ import annotations
 
 from functools import partial
@@ -12,9 +17,11 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from . import modeling_slot, ops
-from .modeling_slot import Block, PatchEmbed, _cfg, get_sinusoid_encoding_table, register_model
+from . import _lib, modeling_slot, ops
+from .functions import DropMaskFn, PatchEmbedFn
+from .modeling_slot import Block, DropoutSource, PatchEmbed, _cfg, get_sinusoid_encoding_table, register_model
 from .ops import ACT_GELU
+from .regions import PoolHeadRegionFn
 from .weight_cache import _WCACHE, _f32
 
 
@@ -24,26 +31,37 @@ class VisionTransformer(nn.Module):
                  drop_path_rate=0., norm_layer=nn.LayerNorm, init_values=0., use_learnable_pos_emb=False, init_scale=0.,
                  all_frames=16, tubelet_size=2, use_checkpoint=False, use_mean_pooling=True, compute_dtype='bf16'):
         super().__init__()
-        if use_mean_pooling:
-            raise NotImplementedError("only the cls-token teacher (use_mean_pooling=False) is on the DEVIAS slot path "
-                                      "(run_slot_finetuning.py:392-406)")
-        if use_learnable_pos_emb or fc_drop_rate or drop_rate or attn_drop_rate:
-            raise NotImplementedError("learnable pos-emb / dropout are not used by the frozen teacher")
+        if use_learnable_pos_emb:
+            raise NotImplementedError("learnable pos-emb is not used by DEVIAS (sinusoid table only)")
+        if use_checkpoint:
+            raise NotImplementedError("use_checkpoint=True: activation checkpointing re-runs a block's forward inside backward, which the fused regions "
+                                      "(one saved arena, ONE backward per forward) do not support; 288 GB hold the activations")
+        for nm, v in (("fc_drop_rate", fc_drop_rate), ("drop_rate", drop_rate), ("attn_drop_rate", attn_drop_rate), ("drop_path_rate", drop_path_rate)):
+            if not 0.0 <= float(v) < 1.0:
+                raise ValueError(f"{nm} must be in [0, 1), got {v}")
+        self.dropout_source = None             # None: DropoutSource() (torch's generators); tests install one with given masks
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
         self.tubelet_size = tubelet_size
+        self.use_mean_pooling = bool(use_mean_pooling)
+        self.use_checkpoint = False
         self.patch_embed = PatchEmbed(img_size=img_size, patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim,
                                       num_frames=all_frames, tubelet_size=tubelet_size)
-        num_patches = self.patch_embed.num_patches + 1
-        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
-        nn.init.trunc_normal_(self.cls_token, std=.02)
+        num_patches = self.patch_embed.num_patches
+        if not use_mean_pooling:
+            self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+            nn.init.trunc_normal_(self.cls_token, std=.02)
+            num_patches += 1
         self.pos_embed = get_sinusoid_encoding_table(num_patches, embed_dim)
+        self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]
         self.blocks = nn.ModuleList([
-            Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
-                  norm_layer=norm_layer, init_values=init_values) for _ in range(depth)])
-        self.norm = norm_layer(embed_dim)
-        self.fc_norm = None
-        self.fc_dropout = nn.Identity()
+            Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop_rate,
+                  attn_drop=attn_drop_rate, drop_path=dpr[i], norm_layer=norm_layer, init_values=init_values) for i in range(depth)])
+        self.norm = nn.Identity() if use_mean_pooling else norm_layer(embed_dim)
+        self.fc_norm = norm_layer(embed_dim) if use_mean_pooling else None
+        self.fc_drop_rate = float(fc_drop_rate)
+        self.fc_dropout = nn.Dropout(p=fc_drop_rate) if fc_drop_rate > 0 else nn.Identity()      # parameter-free container as in the reference (:238); applied in PoolHeadRegionFn
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
         nn.init.trunc_normal_(self.head.weight, std=.02)
         self.apply(self._init_weights)
@@ -68,6 +86,13 @@ class VisionTransformer(nn.Module):
     def no_weight_decay(self):
         return {'pos_embed', 'cls_token'}
 
+    def get_classifier(self):
+        return self.head
+
+    def reset_classifier(self, num_classes, global_pool=''):
+        self.num_classes = num_classes
+        self.head = nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()
+
     def set_compute_dtype(self, compute_dtype):
         self.compute_dtype = {'bf16': torch.bfloat16, 'fp32': torch.float32}[compute_dtype]
         return self
@@ -78,8 +103,14 @@ class VisionTransformer(nn.Module):
             self._pos_cache[key] = self.pos_embed[0].to(device=device, dtype=dtype).contiguous()
         return self._pos_cache[key]
 
-    @torch.no_grad()
     def forward_features(self, x, return_attn=False):
+        """the reference's token (:273-311)"""
+        if self._builds_graph() or self.use_mean_pooling:
+            return self.forward(x, return_attn)[0]
+        return self._frozen_features(x, return_attn)
+
+    @torch.no_grad()
+    def _frozen_features(self, x, return_attn=False):
         if return_attn:
             raise NotImplementedError("per-block attention maps are never materialised by the fused MHSA kernel")
         if not x.is_cuda:
@@ -131,10 +162,64 @@ class VisionTransformer(nn.Module):
         return y
 
     @torch.no_grad()
-    def forward(self, x, return_attn=False):
-        token = self.forward_features(x, return_attn)
+    def _frozen_forward(self, x, return_attn=False):
+        token = self._frozen_features(x, return_attn)
         logits = ops.gemm(token, _WCACHE.get(self.head.weight, self.compute_dtype), bias=_f32(self.head.bias))
         return token, logits
+
+    def _builds_graph(self):
+        return self.training and torch.is_grad_enabled()
+
+    def _pooled_forward(self, x):
+        """PatchEmbedFn -> (cls row) -> Block.run per block -> PoolHeadRegionFn, on the unpadded [B * Nt, D] token matrix.  With autograd on this is the training
+        step's forward; under torch.no_grad() Block.run takes the forward-only region and the head region saves nothing (bitwise the same outputs at zero drop rates)."""
+        if not x.is_cuda:
+            raise RuntimeError("devias_amd.VisionTransformer runs on an MI355X only (HIP kernels; no CPU fallback): move the model and the input to cuda")
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        x = x.contiguous()
+        if not isinstance(self.head, nn.Linear) or self.num_classes < 2 or self.embed_dim not in (384, 768, 1024):
+            raise NotImplementedError(f"the pooled-head region is built for at least 2 classes and widths 384 / 768 / 1024, got {self.num_classes} classes, D={self.embed_dim}")
+        B = x.shape[0]
+        pe = self.patch_embed
+        N, D, cdt = pe.num_patches, self.embed_dim, self.compute_dtype
+        pos = self._pos(x.device, cdt)
+        pmeta = (pe.tubelet_size, pe.patch_size[0], cdt)
+        if self.use_mean_pooling:
+            Nt = N
+            h = PatchEmbedFn.apply(x, pe.proj.weight, pe.proj.bias, pos, pmeta)
+        else:
+            Nt = N + 1
+            key = (str(x.device), cdt, "patches")
+            if key not in self._pos_cache:
+                self._pos_cache[key] = pos[1:].contiguous()
+            tok = PatchEmbedFn.apply(x, pe.proj.weight, pe.proj.bias, self._pos_cache[key], pmeta)
+            cls = (self.cls_token.reshape(1, D).float() + pos[:1].float()).to(cdt)                 # cls FIRST, then + pos (:277-283)
+            h = torch.cat([cls.expand(B, 1, D), tok.view(B, N, D)], dim=1).reshape(B * Nt, D)
+        src = self.dropout_source or DropoutSource()
+        if self.training and self.pos_drop.p > 0:
+            h = DropMaskFn.apply(h, src.element_mask("pos", -1, tuple(h.shape), 1.0 - float(self.pos_drop.p), h.device))
+        for i, blk in enumerate(self.blocks):
+            h = blk.run(h, B, Nt, cdt, i, src)
+        drop_mask = None
+        if self.training and self.fc_drop_rate > 0:
+            keep = 1.0 - self.fc_drop_rate                  # nn.Dropout(fc_drop_rate) on the token (:320): Bernoulli(keep) / keep, drawn like drop_path's masks
+            drop_mask = self.dropout_source.element_mask("head", -2, (B, D), keep, x.device) if self.dropout_source is not None else \
+                ((keep + torch.rand((B, D), device=x.device, dtype=torch.float32)).floor() / keep).contiguous()
+        ln = self.fc_norm if self.use_mean_pooling else self.norm
+        meta = (B, Nt, _lib.POOL_MEAN if self.use_mean_pooling else _lib.POOL_CLS, ln.eps, cdt, torch.is_grad_enabled())      # (read here: inside a Function's forward autograd is always off)
+        args = (h, ln.weight, ln.bias, self.head.weight, self.head.bias, meta)
+        return PoolHeadRegionFn.apply(*args, drop_mask) if drop_mask is not None else PoolHeadRegionFn.apply(*args)
+
+    def forward(self, x, return_attn=False):
+        if return_attn:
+            raise NotImplementedError("per-block attention maps are never materialised by the fused MHSA kernel")
+        if self._builds_graph():
+            return self._pooled_forward(x)
+        if self.use_mean_pooling:
+            with torch.no_grad():
+                return self._pooled_forward(x)
+        return self._frozen_forward(x, return_attn)          # eval() or no_grad in cls-token mode: the frozen teacher's path, tensors without a graph
 
 
 @register_model

@@ -113,6 +113,73 @@ def region_counters() -> dict:
     return {k: int(lib.devias_region_counter(i)) for k, i in _lib.REGION_COUNTERS.items()}
 
 
+def pool_head_args(B: int, Nt: int, pool: int, eps: float, W: torch.Tensor, bias: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor,
+                   drop_mask: Optional[torch.Tensor] = None) -> "_lib.PoolHeadArgs":
+    """devias_pool_head_args for head weight W [C, D] in the compute dtype and fp32 bias / LayerNorm vectors; the workspace is the stream's.  The caller keeps the
+    tensors alive while the struct is in use (it holds raw pointers)."""
+    lib = _lib.load()
+    C, D = W.shape
+    dt = dt_code(W.dtype)
+    _chk(W, "pool_head.W")
+    for n, t, shape in (("bias", bias, (C,)), ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,))):
+        _chk(t, "pool_head." + n, torch.float32)
+        assert tuple(t.shape) == shape, (n, tuple(t.shape), shape)
+    a = _lib.PoolHeadArgs()
+    a.struct_size = ctypes.sizeof(_lib.PoolHeadArgs)
+    a.B, a.Nt, a.D, a.C, a.dtype, a.pool, a.eps = B, Nt, D, C, dt, pool, eps
+    a.W, a.bias, a.ln_w, a.ln_b = W.data_ptr(), bias.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr()
+    if drop_mask is not None:
+        _chk(drop_mask, "pool_head.drop_mask", torch.float32)
+        assert tuple(drop_mask.shape) == (B, D)
+        a.drop_mask = drop_mask.data_ptr()
+    nws = lib.devias_pool_head_workspace_bytes(B, Nt, D, C, dt)
+    if nws <= 0:
+        raise NotImplementedError(f"devias_pool_head: unsupported dims B={B} Nt={Nt} D={D} C={C} (D in 384 / 768 / 1024, B, Nt >= 1, C >= 2)")
+    ws = workspace(nws, W.device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    return a
+
+
+def pool_head_fwd(a: "_lib.PoolHeadArgs", h: torch.Tensor, save: bool = True):
+    """devias_pool_head_fwd: h [B*Nt, D] -> (token [B, D], logits [B, C], the save arena as a uint8 tensor or None)"""
+    lib = _lib.load()
+    _chk(h, "pool_head.h")
+    assert tuple(h.shape) == (a.B * a.Nt, a.D) and dt_code(h.dtype) == a.dtype
+    ws = workspace(a.ws_bytes, h.device)                  # (the stream's workspace may have been re-allocated larger since the struct was filled)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    arena = torch.empty((lib.devias_pool_head_save_bytes(a.B, a.D, a.dtype),), dtype=torch.uint8, device=h.device) if save else None
+    token = torch.empty((a.B, a.D), dtype=h.dtype, device=h.device)
+    logits = torch.empty((a.B, a.C), dtype=h.dtype, device=h.device)
+    _lib.check(lib.devias_pool_head_fwd(ctypes.byref(a), h.data_ptr(), token.data_ptr(), logits.data_ptr(), _p(arena), _stream()), "devias_pool_head_fwd")
+    return token, logits, arena
+
+
+def pool_head_bwd(a: "_lib.PoolHeadArgs", arena: torch.Tensor, dlogits: torch.Tensor, dtoken: Optional[torch.Tensor], dx: torch.Tensor, grads) -> None:
+    """devias_pool_head_bwd: writes every row of dx [B*Nt, D] and the four fp32 gradients `grads` = (dW [C, D], db [C], dln_w [D], dln_b [D])"""
+    lib = _lib.load()
+    _chk(dlogits, "pool_head.dlogits"); _chk(dx, "pool_head.dx")
+    assert tuple(dlogits.shape) == (a.B, a.C) and tuple(dx.shape) == (a.B * a.Nt, a.D) and dt_code(dx.dtype) == a.dtype and dlogits.dtype == dx.dtype
+    if dtoken is not None:
+        _chk(dtoken, "pool_head.dtoken", dx.dtype)
+        assert tuple(dtoken.shape) == (a.B, a.D)
+    g = _lib.PoolHeadGrads()
+    g.struct_size = ctypes.sizeof(_lib.PoolHeadGrads)
+    for t, shape in zip(grads, ((a.C, a.D), (a.C,), (a.D,), (a.D,))):
+        _chk(t, "pool_head.grad", torch.float32)
+        assert tuple(t.shape) == shape
+    g.dW, g.db, g.dln_w, g.dln_b = [t.data_ptr() for t in grads]
+    ws = workspace(a.ws_bytes, dx.device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _lib.check(lib.devias_pool_head_bwd(ctypes.byref(a), arena.data_ptr(), dlogits.data_ptr(), _p(dtoken), dx.data_ptr(), ctypes.byref(g), _stream()),
+               "devias_pool_head_bwd")
+
+
+def pool_head_launches() -> int:
+    """devias_pool_head_fwd / _bwd calls that launched since the last reset (devias_pool_head_launches: a counter of its own, both banks are closed);
+    counters(reset=True) resets it too"""
+    return int(_lib.load().devias_pool_head_launches())
+
+
 def auto_split_k(M: int, N: int, K: int, bk: int = 64) -> int:
     """Split the long reduction of a weight-gradient GEMM so that (tiles x splits) is just under ONE full round of the kernel that will run it:
     2 slots per CU for the bf16 256x256 kernel counted in 256x128 halves (512 on MI355X), 3 per CU for the 128x128 kernel (768); the CU count

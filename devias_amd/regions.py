@@ -297,7 +297,48 @@ class FusionHeadFn(Function):
         return (dslots, None, None, *outs, None, None)
 
 
-_AGG_MATS = ("to_q", "to_k", "to_v", "to_out_w", "ff0_w", "ff3_w")                       # -> devias_agg_layer_params.Wq Wk Wv Wo W1 W2
+class PoolHeadRegionFn(Function):
+    """The plain video ViT's part after the encoder (model/modeling_finetune.py:314-325) as one devias_pool_head_fwd / _bwd call: h [B*Nt, D] ->
+    (token [B, D], logits [B, C]).  meta = (B, Nt, pool, eps, cdt, grad_enabled): pool is _lib.POOL_MEAN (fc_norm(x.mean(1)); ln_w / ln_b are fc_norm's) or
+    _lib.POOL_CLS (norm(x)[:, 0]; ln_w / ln_b are norm's); grad_enabled is the caller's torch.is_grad_enabled(), read BEFORE apply (see FusionHeadFn): where it is
+    False, or no input requires a gradient, nothing is saved (devias_pool_head_fwd with save = NULL; same bits).  drop_mask: optional fp32 [B, D] of 0 / (1 / keep),
+    fc_dropout on the token."""
+
+    @staticmethod
+    def forward(ctx, h, ln_w, ln_b, hw, hb, meta, drop_mask=None):
+        B, Nt, pool, eps, cdt, grad_enabled = meta
+        h = h.contiguous()
+        keep = [_WCACHE.get(hw, cdt), _f32(hb), _f32(ln_w), _f32(ln_b)]
+        a = ops.pool_head_args(B, Nt, pool, eps, *keep, drop_mask)
+        need_bwd = bool(grad_enabled) and any(ctx.needs_input_grad)
+        token, logits, save = ops.pool_head_fwd(a, h, save=need_bwd)
+        if need_bwd:
+            ctx.args = a
+            ctx.keep = (keep, save, h, drop_mask)
+            ctx.x_version = h._version
+            ctx.params = (ln_w, ln_b, hw, hb)
+        else:
+            ctx.keep = ctx.args = None
+        return token, logits
+
+    @staticmethod
+    def backward(ctx, dtoken, dlogits):
+        _region_state(ctx, "PoolHeadRegionFn", ctx.keep[2] if ctx.keep is not None else None)
+        a = ctx.args
+        keep, save, h, drop_mask = ctx.keep
+        ln_w, ln_b, hw, hb = ctx.params
+        dev = h.device
+        dlogits = dlogits.contiguous() if dlogits is not None else torch.zeros((a.B, a.C), dtype=h.dtype, device=dev)
+        dtoken = dtoken.contiguous() if dtoken is not None else None
+        gd = _GradDest([(p, tuple(p.shape)) for p in (hw, hb, ln_w, ln_b)], dev)
+        dx = torch.empty_like(h)
+        ops.pool_head_bwd(a, save, dlogits, dtoken, dx, gd.out)
+        ctx.keep = ctx.args = None
+        dW, db, dlw, dlb = gd.out
+        return (dx, dlw, dlb, dW, db, None, None)
+
+
+_AGG_MATS = ("to_q", "to_k", "to_v", "to_out_w", "ff0_w", "ff3_w")                      # -> devias_agg_layer_params.Wq Wk Wv Wo W1 W2
 _AGG_VECS = ("to_out_b", "norm_w", "norm_b", "ctx_w", "ctx_b", "ff0_b", "ff3_b", "ffn_w", "ffn_b")   # -> bo norm_w norm_b ctx_w ctx_b b1 b2 ffn_w ffn_b
 # (devias_agg_layer_grads -- dWq dWk dWv dWo dbo dnorm_w dnorm_b dctx_w dctx_b dW1 db1 dW2 db2 dffn_w dffn_b -- is in _LAYER_KEYS order)
 

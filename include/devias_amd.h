@@ -54,6 +54,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     173 = devias_encoder_block_infer, devias_encoder_block_infer_workspace_bytes, DEVIAS_CNT_BLOCK_INFER (additive),
                                     174 = devias_adamw_step, devias_adamw_multi, devias_adamw_ema_multi take beta1 / beta2 as double (recompile callers),
                                     175 = devias_fusion_head_* (the slot-fusion classifier's head region), devias_softmax_ce_*, devias_region_counter (additive),
+                                    176 = devias_pool_head_* (the plain video ViT's pooled-head region), devias_pool_head_launches (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -726,6 +727,49 @@ int64_t devias_softmax_ce_workspace_bytes(int32_t B);
 int devias_softmax_ce_fwd(const void* logits, const int64_t* target, int32_t B, int32_t C, int32_t dtype, float smoothing, float* loss, float* ws, void* stream);
 int devias_softmax_ce_bwd(const void* logits, const int64_t* target, int32_t B, int32_t C, int32_t dtype, float smoothing, const float* g_loss, void* dlogits, void* stream);
 int64_t devias_region_counter(int32_t id);      /* DEVIAS_RCNT_* */
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 176: the plain video ViT's part after the encoder (model/modeling_finetune.py: fc_norm(x.mean(1)) or norm(x)[:, 0], fc_dropout, head), one call per direction.
+ *   h T [B*Nt, D], unpadded (exactly B*Nt rows), T = bf16 or fp32
+ *   t[b]      = sum over the Nt token rows of clip b (fp32; chunks of DEVIAS_POOL_HEAD_CHUNK tokens, one workgroup each, their fp32 sums kept in the workspace and
+ *               added in chunk order) * fl(1/Nt) -- a multiplication by the rounded reciprocal, not a division          (pool = DEVIAS_POOL_MEAN)
+ *             = row 0 of clip b                                                                                          (pool = DEVIAS_POOL_CLS)
+ *   y[b]      = LN(t[b]; ln_w, ln_b, eps), two-pass fp32 statistics            (fc_norm in MEAN mode, norm in CLS mode: only row 0 of norm(x) is ever used)
+ *   token[b]  = T(y[b])                                                        T [B, D]
+ *   a[b]      = T(y[b] * drop_mask[b])  (the mask meets the unrounded y)       T [B, D], saved
+ *   logits    = T(a W^T + bias)                                                T [B, C]
+ * Backward, from dlogits T [B, C] and an optional dtoken T [B, D]: dW = dlogits^T a, db = column sums of dlogits (fp32, written, not accumulated); da = dlogits W kept in
+ * fp32; g = da * drop_mask + dtoken; dln_w = sum_b g x^, dln_b = sum_b g (per-clip partials summed over the clips in index order); the LayerNorm's input gradient,
+ * times fl(1/Nt) in MEAN mode, is rounded to T ONCE per clip and written into every token row of the clip (MEAN) or into row 0 with zeros in the other rows (CLS):
+ * the call writes all B*Nt rows of dx.  No atomics: results are bitwise equal run to run.
+ * Both structs start with struct_size = sizeof(the struct): a mismatch is DEVIAS_EINVAL, like a null pointer, a bad dtype / pool or a short workspace -- all before
+ * anything is launched.  Supported: D in {384, 768, 1024}, B >= 1, Nt >= 1 (B*Nt < 2^31), C >= 2; anything else is DEVIAS_EUNSUPPORTED (the size queries then return 0).
+ * devias_pool_head_launches(): _fwd / _bwd calls that passed validation and launched since the last devias_counters_reset() (a counter of its own: both banks are closed).
+ * ------------------------------------------------------------------------------------------------- */
+#define DEVIAS_POOL_MEAN 0
+#define DEVIAS_POOL_CLS 1
+#define DEVIAS_POOL_HEAD_CHUNK 64        /* token rows one workgroup of the two streaming kernels covers */
+typedef struct {
+    int32_t struct_size;                 /* sizeof(devias_pool_head_args) */
+    int32_t B, Nt, D, C, dtype, pool;
+    float eps;                           /* the model's norm_layer: 1e-6 */
+    const void* W;                       /* T: head [C, D] */
+    const float *bias, *ln_w, *ln_b;     /* head.bias [C]; fc_norm (MEAN) or norm (CLS) weight / bias [D] */
+    const float* drop_mask;              /* optional fp32 [B, D], 0 or 1/keep: fc_dropout on the token */
+    float* ws; int64_t ws_bytes;         /* devias_pool_head_workspace_bytes() */
+} devias_pool_head_args;
+typedef struct {
+    int32_t struct_size;                 /* sizeof(devias_pool_head_grads) */
+    int32_t reserved;
+    float *dW, *db, *dln_w, *dln_b;      /* fp32, written (not accumulated) */
+} devias_pool_head_grads;
+int64_t devias_pool_head_workspace_bytes(int32_t B, int32_t Nt, int32_t D, int32_t C, int32_t dtype);
+int64_t devias_pool_head_save_bytes(int32_t B, int32_t D, int32_t dtype);
+/* save: devias_pool_head_save_bytes() bytes for the backward, or NULL where nobody will ask for one (x^, rstd and a then live in the workspace; same bits).  Layout of
+ * save, each piece rounded up to 256 bytes: x^ fp32 [B, D]; rstd fp32 [B]; a T [B, D]. */
+int devias_pool_head_fwd(const devias_pool_head_args* a, const void* h, void* token, void* logits, void* save, void* stream);
+int devias_pool_head_bwd(const devias_pool_head_args* a, const void* save, const void* dlogits, const void* dtoken, void* dx, const devias_pool_head_grads* g, void* stream);
+int64_t devias_pool_head_launches(void);
 
 /* Final LayerNorm + AggregationBlock with the folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:105-139;
  * agg_block/attention.py:29-40,66-72,108-141): `depth` layers over `tied ? 1 : depth` weight sets; S <= 4 slots. */
