@@ -22,7 +22,6 @@ extern "C" int64_t devias_counter(int32_t id) { return (id >= 0 && id < DEVIAS_C
 static std::atomic<int64_t> g_rcnt[DEVIAS_RCNT_MAX];      // the second bank (ABI 175): fused regions / loss entry points
 void devias_count_region(int id) { if (id >= 0 && id < DEVIAS_RCNT_MAX) g_rcnt[id].fetch_add(1, std::memory_order_relaxed); }
 extern "C" int64_t devias_region_counter(int32_t id) { return (id >= 0 && id < DEVIAS_RCNT_MAX) ? g_rcnt[id].load(std::memory_order_relaxed) : -1; }
-void devias_pool_head_counter_reset();      // pool_head.hip: the call counter behind devias_pool_head_launches (ABI 176; both banks are closed)
 extern "C" void devias_counters_reset(void) {
     for (int i = 0; i < DEVIAS_CNT_MAX; ++i) g_cnt[i].store(0, std::memory_order_relaxed);
     for (int i = 0; i < DEVIAS_RCNT_MAX; ++i) g_rcnt[i].store(0, std::memory_order_relaxed);

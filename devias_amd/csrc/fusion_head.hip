@@ -8,8 +8,9 @@
 //
 // What the chain is bound by: B workgroups (12 in the recipe) on 256 CUs and two dozen dependent launches -- the number of launches and the host that issues them,
 // not bandwidth or arithmetic (a [12, 768] row set is 18 KB).  So the new kernels are one workgroup per row with strided scalar loads (D / 256 <= 4 elements per lane, all in
-// registers, no scratch), every statistic a two-pass fp32 block reduction (DPP wave sums + a 4-wave LDS combine), and the GEMMs / weight gradients / column sums
-// go through the library's small-M launchers as csrc/regions.hip does.  No atomics: the per-clip partial sums of the four LayerNorm parameter pairs are reduced
+// registers, no scratch), every statistic a two-pass fp32 block reduction (row_kernels.h: the block reductions and the row LayerNorm's pieces, shared with loss.hip
+// and pool_head.hip), and the GEMMs / weight gradients / column sums go through the library's small-M launchers as csrc/regions.hip does (region_host.h: those calls,
+// the arena carver, the entry points' checks and dtype dispatch).  No atomics: the per-clip partial sums of the four LayerNorm parameter pairs are reduced
 // over the clips in index order by one launch (devias_flush_deferred), so results are bitwise equal run to run.
 //
 // The pre-trained head only selects: Z is not differentiated (head.weight / head.bias get no gradient), fc_scene_down / fc_scene_ln are never read (the reference
@@ -17,37 +18,10 @@
 #include "common.h"
 #include <string.h>
 #include "roctx_shim.h"
-#include "region_host.h"
-
-void devias_count_region(int id);      // api.hip: DEVIAS_RCNT_*
+#include "region_host.h"      // split policies, GEMM / weight-gradient calls, the arena carver, argument checks, dispatch_t
+#include "row_kernels.h"       // NT, EPT, block reductions, the row LayerNorm's statistics and backward means, row_stats
 
 namespace {
-
-enum { NT = 256, EPT = 4 };          // threads per workgroup; elements per thread (D <= 1024)
-
-__device__ __forceinline__ float block_sum(float v, float* sm /*[4]*/) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sm[0] + sm[1] + sm[2] + sm[3];
-}
-// two sums with one pair of barriers
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* sm /*[8]*/) {
-    a = wave_sum(a); b = wave_sum(b);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = a; sm[4 + (threadIdx.x >> 6)] = b; }
-    __syncthreads();
-    a = sm[0] + sm[1] + sm[2] + sm[3];
-    b = sm[4] + sm[5] + sm[6] + sm[7];
-}
-__device__ __forceinline__ float block_max(float v, float* sm) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-}
 
 // ---- gather + action_norm / scene_norm (modeling_slot_fusion.py:391-395) ---------------------------------------------------------------
 // row 2b + t of `input` viewed [2B, D] (t = 0: action, 1: scene) = LN(X[b, idx[b, t]]; norm_t).  Statistics two-pass in fp32 (rows with a common offset).
@@ -62,14 +36,10 @@ __global__ __launch_bounds__(NT) void fusion_gather_ln_fwd_kernel(const T* __res
     const T* x = X + ((int64_t)b * S + s) * D;
     const float* gw = t ? sw : aw;
     const float* gb = t ? sb : ab;
-    float v[EPT], q = 0.f;
+    float v[EPT], mean, rstd;
 #pragma unroll
-    for (int i = 0; i < EPT; ++i) { const int k = threadIdx.x + NT * i; v[i] = k < D ? to_f32(x[k]) : 0.f; q += v[i]; }
-    const float mean = block_sum(q, sm) / (float)D;
-    q = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) { const int k = threadIdx.x + NT * i; const float d = k < D ? v[i] - mean : 0.f; q += d * d; }
-    const float rstd = rsqrtf(block_sum(q, sm) / (float)D + eps);
+    for (int i = 0; i < EPT; ++i) { const int k = threadIdx.x + NT * i; v[i] = k < D ? to_f32(x[k]) : 0.f; }
+    row_ln_stats(v, D, eps, sm, mean, rstd);
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int k = threadIdx.x + NT * i;
@@ -111,10 +81,9 @@ __global__ __launch_bounds__(NT) void fusion_gather_ln_bwd_kernel(const T* __res
                 c1 += gy[i]; c2 += gy[i] * xh[i];
             }
         }
-        block_sum2(c1, c2, sm);
-        c1 /= (float)D; c2 /= (float)D;
+        row_ln_bwd_means(c1, c2, D, sm);
 #pragma unroll
-        for (int i = 0; i < EPT; ++i) acc[i] += rstd * (gy[i] - c1 - xh[i] * c2);
+        for (int i = 0; i < EPT; ++i) acc[i] += row_ln_dx(gy[i], xh[i], rstd, c1, c2);
     }
 #pragma unroll
     for (int i = 0; i < EPT; ++i) { const int k = threadIdx.x + NT * i; if (k < D) dslots[(int64_t)blockIdx.x * D + k] = from_f32<T>(acc[i]); }
@@ -129,6 +98,7 @@ __global__ __launch_bounds__(NT) void fusion_mid_fwd_kernel(const T* __restrict_
                                                             T* __restrict__ r, float* __restrict__ stat) {
     __shared__ float sm[8];
     const int b = blockIdx.x, Dh = D >> 1;
+    // (the statistics of the two half rows stay written out: they share each pair of barriers through block_sum2, which row_ln_stats would need a flag for)
     float v[EPT], q0 = 0.f, q1 = 0.f;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -146,22 +116,15 @@ __global__ __launch_bounds__(NT) void fusion_mid_fwd_kernel(const T* __restrict_
     }
     block_sum2(q0, q1, sm);
     const float r0 = rsqrtf(q0 / (float)Dh + eps), r1 = rsqrtf(q1 / (float)Dh + eps);
-    float h[EPT], q = 0.f;
+    float h[EPT];
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int k = threadIdx.x + NT * i;
         h[i] = 0.f;
         if (k < D) { const int j = k < Dh ? k : k - Dh; h[i] = (v[i] - (k < Dh ? m0 : m1)) * (k < Dh ? r0 : r1) * lw[j] + lb[j]; }
-        q += h[i];
     }
     float mi = 0.f, ri = 1.f;
-    if constexpr (IN_LN) {
-        mi = block_sum(q, sm) / (float)D;
-        q = 0.f;
-#pragma unroll
-        for (int i = 0; i < EPT; ++i) { const int k = threadIdx.x + NT * i; const float d = k < D ? h[i] - mi : 0.f; q += d * d; }
-        ri = rsqrtf(block_sum(q, sm) / (float)D + eps);
-    }
+    if constexpr (IN_LN) row_ln_stats(h, D, eps, sm, mi, ri);
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int k = threadIdx.x + NT * i;
@@ -212,18 +175,17 @@ __global__ __launch_bounds__(NT) void fusion_mid_bwd_kernel(const T* __restrict_
         }
     }
     if constexpr (IN_LN) {
-        block_sum2(c1, c2, sm);
-        c1 /= (float)D; c2 /= (float)D;
+        row_ln_bwd_means(c1, c2, D, sm);
 #pragma unroll
         for (int i = 0; i < EPT; ++i) {
             const int k = threadIdx.x + NT * i;
             if (k < D) {
-                g[i] = ri * (g[i] - c1 - xh[i] * c2);
+                g[i] = row_ln_dx(g[i], xh[i], ri, c1, c2);
                 xh[i] = (to_f32(u[(int64_t)b * D + k]) - (k < Dh ? m0 : m1)) * (k < Dh ? r0 : r1);
             }
         }
     }
-    // the two half-row LayerNorms (one parameter pair, two rows)
+    // the two half-row LayerNorms (one parameter pair, two rows): written out, their four means take two block_sum2 where row_ln_bwd_means would take a half-row flag
     float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -285,12 +247,8 @@ __global__ __launch_bounds__(NT) void softmax_ce_bwd_kernel(const T* __restrict_
         for (int c = threadIdx.x; c < C; c += NT) dz[c] = from_f32<T>(0.f);
         return;
     }
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < C; c += NT) m = fmaxf(m, to_f32(z[c]));
-    const float mx = block_max(m, sm);
-    float s = 0.f;
-    for (int c = threadIdx.x; c < C; c += NT) s += expf(to_f32(z[c]) - mx);
-    const float lse = mx + logf(block_sum(s, sm));
+    float mx, lse;
+    row_stats(z, C, sm, mx, lse);
     const float g = g_loss[0] / (float)B, off = eps / (float)C;
     for (int c = threadIdx.x; c < C; c += NT)
         dz[c] = from_f32<T>(g * (expf(to_f32(z[c]) - lse) - (c == (int)y ? 1.f - eps : 0.f) - off));
@@ -303,7 +261,7 @@ int gemm_b(const Ctx& c, const void* A, const void* Bm, void* C, int M, int N, i
 }
 
 inline bool dims_supported(int B, int S, int D, int nb, int ns, int Cd) {
-    return B >= 1 && (int64_t)B * 4 * 1024 < 0x7fffffff && S >= 1 && S <= 4 && (D == 384 || D == 768 || D == 1024) && nb >= 1 && ns >= 1 && Cd >= 2;
+    return B >= 1 && (int64_t)B * 4 * 1024 < 0x7fffffff && S >= 1 && S <= 4 && row_dim_ok(D) && nb >= 1 && ns >= 1 && Cd >= 2;
 }
 int64_t kernel_ws_bytes(int B, int S, int D, int C, int Cd, int dtype) {
     const int R = B * S, Dh = D / 2;
@@ -313,44 +271,34 @@ int64_t kernel_ws_bytes(int B, int S, int D, int C, int Cd, int dtype) {
     w = max64(w, max64(devias_colsum_workspace_bytes(B, Cd), devias_colsum_workspace_bytes(2 * B, Dh)));
     return al256(w) + 256;
 }
-// what lives behind the kernels' workspace: Z; the forward's u / r / statistics where nothing is saved; the backward's temporaries and partial sums
-struct Tmp {
-    char *Z, *u, *r, *dr, *du, *dinp;
-    float *stat_g, *stat_m, *p_in, *p_lw, *p_lb, *p_n;
-    int64_t bytes;
-    Tmp(void* base, int B, int S, int D, int C, int dtype) {
-        const int64_t es = esize(dtype);
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);
-        auto take = [&](int64_t n) { char* q = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return q; };
-        Z = take((int64_t)B * S * C * es);
-        u = take((int64_t)B * D * es); r = take((int64_t)B * D * es);
-        stat_g = (float*)take((int64_t)B * 4 * 4); stat_m = (float*)take((int64_t)B * 6 * 4);
-        dr = take((int64_t)B * D * es); du = take((int64_t)B * D * es); dinp = take((int64_t)2 * B * D * es);
-        p_in = (float*)take((int64_t)B * 2 * D * 4); p_lw = (float*)take((int64_t)B * D * 4); p_lb = (float*)take((int64_t)B * D * 4);
-        p_n = (float*)take((int64_t)4 * B * D * 4);
-        bytes = off;
-    }
-};
+// what backward reads of the forward: the middle chain's input and output, the statistics of the gather's and the middle chain's LayerNorms
 struct Save {
     char *u, *r; float *stat_g, *stat_m;
-    int64_t bytes;
-    Save(void* base, int B, int D, int dtype) {
+    Save(Arena& ar, int B, int D, int dtype) {
         const int64_t es = esize(dtype);
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);
-        auto take = [&](int64_t n) { char* q = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return q; };
-        u = take((int64_t)B * D * es); r = take((int64_t)B * D * es);
-        stat_g = (float*)take((int64_t)B * 4 * 4); stat_m = (float*)take((int64_t)B * 6 * 4);
-        bytes = off;
+        u = ar.take((int64_t)B * D * es); r = ar.take((int64_t)B * D * es);
+        stat_g = (float*)ar.take((int64_t)B * 4 * 4); stat_m = (float*)ar.take((int64_t)B * 6 * 4);
+    }
+};
+// what lives behind the kernels' workspace: Z; a Save of its own, which the forward writes where the caller keeps none; the backward's temporaries and partial sums
+struct Tmp {
+    char* Z; Save s;          // (carved in this order)
+    char *dr, *du, *dinp;
+    float *p_in, *p_lw, *p_lb, *p_n;
+    int64_t bytes;
+    Tmp(Arena ar, int B, int S, int D, int C, int dtype) : Z(ar.take((int64_t)B * S * C * esize(dtype))), s(ar, B, D, dtype) {
+        const int64_t es = esize(dtype);
+        dr = ar.take((int64_t)B * D * es); du = ar.take((int64_t)B * D * es); dinp = ar.take((int64_t)2 * B * D * es);
+        p_in = (float*)ar.take((int64_t)B * 2 * D * 4); p_lw = (float*)ar.take((int64_t)B * D * 4); p_lb = (float*)ar.take((int64_t)B * D * 4);
+        p_n = (float*)ar.take((int64_t)4 * B * D * 4);
+        bytes = ar.off;
     }
 };
 
 int fusion_check(const devias_fusion_args* a, const char* who) {
     DEVIAS_REQUIRE(a, "%s: null args", who);
-    DEVIAS_REQUIRE(a->struct_size == (int32_t)sizeof(devias_fusion_args), "%s: devias_fusion_args.struct_size is %d, this library's struct has %d bytes (recompile the caller)", who,
-                   a->struct_size, (int)sizeof(devias_fusion_args));
-    DEVIAS_REQUIRE(a->dtype == DEVIAS_BF16 || a->dtype == DEVIAS_F32, "%s: bad dtype %d", who, a->dtype);
+    REQUIRE_STRUCT_SIZE(a, devias_fusion_args, who);
+    DEVIAS_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype %d", who, a->dtype);
     if (!dims_supported(a->B, a->S, a->D, a->nb, a->ns, a->Cd))
         return devias_set_error(DEVIAS_EUNSUPPORTED, "%s: unsupported dims B=%d S=%d D=%d nb=%d ns=%d Cd=%d (D in {384, 768, 1024}, 1 <= S <= 4, Cd >= 2, B >= 1, nb, ns >= 1)", who,
                                 a->B, a->S, a->D, a->nb, a->ns, a->Cd);
@@ -365,12 +313,14 @@ int fusion_check(const devias_fusion_args* a, const char* who) {
 }  // namespace
 
 extern "C" int64_t devias_fusion_head_workspace_bytes(int32_t B, int32_t S, int32_t D, int32_t C, int32_t Cd, int32_t dtype) {
-    if (!dims_supported(B, S, D, 1, C > 1 ? C - 1 : 0, Cd) || (dtype != DEVIAS_BF16 && dtype != DEVIAS_F32)) return 0;
-    return kernel_ws_bytes(B, S, D, C, Cd, dtype) + Tmp(nullptr, B, S, D, C, dtype).bytes;
+    if (!dims_supported(B, S, D, 1, C > 1 ? C - 1 : 0, Cd) || !dtype_ok(dtype)) return 0;
+    return kernel_ws_bytes(B, S, D, C, Cd, dtype) + Tmp(Arena(nullptr), B, S, D, C, dtype).bytes;
 }
 extern "C" int64_t devias_fusion_head_save_bytes(int32_t B, int32_t D, int32_t dtype) {
-    if (B < 1 || !(D == 384 || D == 768 || D == 1024) || (dtype != DEVIAS_BF16 && dtype != DEVIAS_F32)) return 0;
-    return Save(nullptr, B, D, dtype).bytes;
+    if (B < 1 || !row_dim_ok(D) || !dtype_ok(dtype)) return 0;
+    Arena ar(nullptr);
+    Save(ar, B, D, dtype);          // (carved at address 0: the arena ends at its size)
+    return ar.off;
 }
 
 extern "C" int devias_fusion_head_fwd(const devias_fusion_args* a, const void* slots, void* input, void* out, int32_t* idx, void* save, void* stream) {
@@ -382,25 +332,26 @@ extern "C" int devias_fusion_head_fwd(const devias_fusion_args* a, const void* s
     hipStream_t st = (hipStream_t)stream;
     const int64_t kw = kernel_ws_bytes(B, S, D, C, Cd, a->dtype);
     const Ctx c{a->dtype, a->ws, kw, nullptr, 0, stream};
-    const Tmp t(reinterpret_cast<char*>(a->ws) + kw, B, S, D, C, a->dtype);
-    char *u = t.u, *r = t.r; float *sg = t.stat_g, *smid = t.stat_m;
-    if (save) { const Save s(save, B, D, a->dtype); u = s.u; r = s.r; sg = s.stat_g; smid = s.stat_m; }
+    const Tmp t(Arena(reinterpret_cast<char*>(a->ws) + kw), B, S, D, C, a->dtype);
+    Arena own(save);
+    const Save s = save ? Save(own, B, D, a->dtype) : t.s;          // the caller's arena, or (nothing to keep) the one in the workspace
     devias_range rg("fusion_head_fwd");
     devias_count_region(DEVIAS_RCNT_FUSION_HEAD);
     RUN(gemm_b(c, slots, a->Wh, t.Z, R, C, D, D, D, 0, a->bh, nullptr));                       // the frozen head: selection only
     RUN(devias_slot_select(t.Z, a->dtype, B, S, C, a->nb, idx, stream));
-    if (a->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((fusion_gather_ln_fwd_kernel<bf16>), dim3(2 * B), dim3(NT), 0, st, (const bf16*)slots, idx, S, D, a->eps_norm, a->an_w, a->an_b, a->sn_w, a->sn_b, (bf16*)input, sg);
-    else
-        hipLaunchKernelGGL((fusion_gather_ln_fwd_kernel<float>), dim3(2 * B), dim3(NT), 0, st, (const float*)slots, idx, S, D, a->eps_norm, a->an_w, a->an_b, a->sn_w, a->sn_b, (float*)input, sg);
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((fusion_gather_ln_fwd_kernel<T>), dim3(2 * B), dim3(NT), 0, st, (const T*)slots, idx, S, D, a->eps_norm, a->an_w, a->an_b, a->sn_w, a->sn_b, (T*)input, s.stat_g);
+    });
     DEVIAS_CHECK_LAUNCH("devias_fusion_head_fwd(gather)");
-    RUN(gemm_b(c, input, a->Wd, u, 2 * B, Dh, D, D, D, 0, a->bd, nullptr));                    // fc_action_down on both tokens: [2B, D/2] == [B, D]
-#define MID_FWD(T, LN) hipLaunchKernelGGL((fusion_mid_fwd_kernel<T, LN>), dim3(B), dim3(NT), 0, st, (const T*)u, D, a->eps_ln, a->ln_w, a->ln_b, a->in_w, a->in_b, a->drop_mask, (T*)r, smid)
-    if (a->dtype == DEVIAS_BF16) { if (a->use_input_ln) MID_FWD(bf16, true); else MID_FWD(bf16, false); }
-    else { if (a->use_input_ln) MID_FWD(float, true); else MID_FWD(float, false); }
-#undef MID_FWD
+    RUN(gemm_b(c, input, a->Wd, s.u, 2 * B, Dh, D, D, D, 0, a->bd, nullptr));                  // fc_action_down on both tokens: [2B, D/2] == [B, D]
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((a->use_input_ln ? fusion_mid_fwd_kernel<T, true> : fusion_mid_fwd_kernel<T, false>), dim3(B), dim3(NT), 0, st, (const T*)s.u, D, a->eps_ln, a->ln_w,
+                           a->ln_b, a->in_w, a->in_b, a->drop_mask, (T*)s.r, s.stat_m);
+    });
     DEVIAS_CHECK_LAUNCH("devias_fusion_head_fwd(middle)");
-    RUN(gemm_b(c, r, a->Wc, out, B, Cd, D, D, D, 0, a->bc, nullptr));
+    RUN(gemm_b(c, s.r, a->Wc, out, B, Cd, D, D, D, 0, a->bc, nullptr));
     return DEVIAS_OK;
 }
 
@@ -409,16 +360,16 @@ extern "C" int devias_fusion_head_bwd(const devias_fusion_args* a, const void* s
     const char* who = "devias_fusion_head_bwd";
     RUN(fusion_check(a, who));
     DEVIAS_REQUIRE(slots && idx && input && save && dout && dslots && g && aligned16(save), "%s: null pointer (slots / idx / input / save / dout / dslots / grads)", who);
-    DEVIAS_REQUIRE(g->struct_size == (int32_t)sizeof(devias_fusion_grads), "%s: devias_fusion_grads.struct_size is %d, this library's struct has %d bytes (recompile the caller)", who,
-                   g->struct_size, (int)sizeof(devias_fusion_grads));
+    REQUIRE_STRUCT_SIZE(g, devias_fusion_grads, who);
     DEVIAS_REQUIRE(g->dan_w && g->dan_b && g->dsn_w && g->dsn_b && g->dWd && g->dbd && g->dln_w && g->dln_b && g->dWc && g->dbc && (!a->use_input_ln || (g->din_w && g->din_b)),
                    "%s: null gradient destination", who);
     const int B = a->B, S = a->S, D = a->D, Dh = D / 2, C = a->nb + a->ns, Cd = a->Cd;
     hipStream_t st = (hipStream_t)stream;
     const int64_t kw = kernel_ws_bytes(B, S, D, C, Cd, a->dtype);
     const Ctx c{a->dtype, a->ws, kw, nullptr, 0, stream};
-    const Tmp t(reinterpret_cast<char*>(a->ws) + kw, B, S, D, C, a->dtype);
-    const Save s(const_cast<void*>(save), B, D, a->dtype);
+    const Tmp t(Arena(reinterpret_cast<char*>(a->ws) + kw), B, S, D, C, a->dtype);
+    Arena own(save);
+    const Save s(own, B, D, a->dtype);
     devias_range rg("fusion_head_bwd");
     devias_count_region(DEVIAS_RCNT_FUSION_HEAD);
     // classifier
@@ -426,21 +377,21 @@ extern "C" int devias_fusion_head_bwd(const devias_fusion_args* a, const void* s
     RUN(colsum(c, dout, B, Cd, g->dbc));
     RUN(gemm_b(c, dout, a->Wc, t.dr, B, D, Cd, Cd, D, 1, nullptr, nullptr));
     // middle chain
-#define MID_BWD(T, LN) hipLaunchKernelGGL((fusion_mid_bwd_kernel<T, LN>), dim3(B), dim3(NT), 0, st, (const T*)t.dr, (const T*)s.r, (const T*)s.u, s.stat_m, D, a->ln_w, a->ln_b, a->in_w, \
-                                          a->drop_mask, (T*)t.du, t.p_in, t.p_lw, t.p_lb)
-    if (a->dtype == DEVIAS_BF16) { if (a->use_input_ln) MID_BWD(bf16, true); else MID_BWD(bf16, false); }
-    else { if (a->use_input_ln) MID_BWD(float, true); else MID_BWD(float, false); }
-#undef MID_BWD
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((a->use_input_ln ? fusion_mid_bwd_kernel<T, true> : fusion_mid_bwd_kernel<T, false>), dim3(B), dim3(NT), 0, st, (const T*)t.dr, (const T*)s.r,
+                           (const T*)s.u, s.stat_m, D, a->ln_w, a->ln_b, a->in_w, a->drop_mask, (T*)t.du, t.p_in, t.p_lw, t.p_lb);
+    });
     DEVIAS_CHECK_LAUNCH("devias_fusion_head_bwd(middle)");
     // down projection on the 2B rows
     RUN(wgrad(c, t.du, input, g->dWd, 2 * B, Dh, D));
     RUN(colsum(c, t.du, 2 * B, Dh, g->dbd));
     RUN(gemm_b(c, t.du, a->Wd, t.dinp, 2 * B, D, Dh, Dh, D, 1, nullptr, dinput));              // + the gradient arriving on the returned `input`, if any
     // scatter through the two norms into the selected slot rows
-    if (a->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((fusion_gather_ln_bwd_kernel<bf16>), dim3(B * S), dim3(NT), 0, st, (const bf16*)slots, idx, (const bf16*)t.dinp, s.stat_g, B, S, D, a->an_w, a->sn_w, (bf16*)dslots, t.p_n);
-    else
-        hipLaunchKernelGGL((fusion_gather_ln_bwd_kernel<float>), dim3(B * S), dim3(NT), 0, st, (const float*)slots, idx, (const float*)t.dinp, s.stat_g, B, S, D, a->an_w, a->sn_w, (float*)dslots, t.p_n);
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((fusion_gather_ln_bwd_kernel<T>), dim3(B * S), dim3(NT), 0, st, (const T*)slots, idx, (const T*)t.dinp, s.stat_g, B, S, D, a->an_w, a->sn_w, (T*)dslots, t.p_n);
+    });
     DEVIAS_CHECK_LAUNCH("devias_fusion_head_bwd(gather)");
     // the four LayerNorm parameter pairs: per-clip partials summed over the clips in index order, ONE launch
     DeviasDeferList dl; dl.n = 0;
@@ -460,7 +411,7 @@ extern "C" int devias_fusion_head_bwd(const devias_fusion_args* a, const void* s
 namespace {
 int ce_check(const char* who, const void* logits, const int64_t* target, int B, int C, int dtype, float eps) {
     DEVIAS_REQUIRE(logits && target, "%s: null logits / target", who);
-    DEVIAS_REQUIRE(dtype == DEVIAS_BF16 || dtype == DEVIAS_F32, "%s: bad dtype %d", who, dtype);
+    DEVIAS_REQUIRE(dtype_ok(dtype), "%s: bad dtype %d", who, dtype);
     DEVIAS_REQUIRE(B >= 1 && C >= 2, "%s: bad dims B=%d C=%d (B >= 1, C >= 2)", who, B, C);
     DEVIAS_REQUIRE(eps >= 0.f && eps < 1.f, "%s: smoothing must be in [0, 1), got %g", who, (double)eps);
     return DEVIAS_OK;
@@ -475,8 +426,10 @@ extern "C" int devias_softmax_ce_fwd(const void* logits, const int64_t* target, 
     DEVIAS_REQUIRE(loss && ws, "%s: null loss / ws", who);
     hipStream_t st = (hipStream_t)stream;
     devias_count_region(DEVIAS_RCNT_SOFTMAX_CE);
-    if (dtype == DEVIAS_BF16) hipLaunchKernelGGL((softmax_ce_fwd_kernel<bf16>), dim3(B), dim3(NT), 0, st, (const bf16*)logits, target, C, smoothing, ws);
-    else hipLaunchKernelGGL((softmax_ce_fwd_kernel<float>), dim3(B), dim3(NT), 0, st, (const float*)logits, target, C, smoothing, ws);
+    dispatch_t(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((softmax_ce_fwd_kernel<T>), dim3(B), dim3(NT), 0, st, (const T*)logits, target, C, smoothing, ws);
+    });
     DEVIAS_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(softmax_ce_final_kernel, dim3(1), dim3(64), 0, st, ws, B, loss);
     DEVIAS_CHECK_LAUNCH("devias_softmax_ce_fwd(final)");
@@ -490,8 +443,10 @@ extern "C" int devias_softmax_ce_bwd(const void* logits, const int64_t* target, 
     DEVIAS_REQUIRE(g_loss && dlogits, "%s: null g_loss / dlogits", who);
     hipStream_t st = (hipStream_t)stream;
     devias_count_region(DEVIAS_RCNT_SOFTMAX_CE);
-    if (dtype == DEVIAS_BF16) hipLaunchKernelGGL((softmax_ce_bwd_kernel<bf16>), dim3(B), dim3(NT), 0, st, (const bf16*)logits, target, B, C, smoothing, g_loss, (bf16*)dlogits);
-    else hipLaunchKernelGGL((softmax_ce_bwd_kernel<float>), dim3(B), dim3(NT), 0, st, (const float*)logits, target, B, C, smoothing, g_loss, (float*)dlogits);
+    dispatch_t(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((softmax_ce_bwd_kernel<T>), dim3(B), dim3(NT), 0, st, (const T*)logits, target, B, C, smoothing, g_loss, (T*)dlogits);
+    });
     DEVIAS_CHECK_LAUNCH(who);
     return DEVIAS_OK;
 }

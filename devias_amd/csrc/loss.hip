@@ -1,30 +1,17 @@
 // Slot selection + TrainLoss ('matching', scene criterion KL or CE) for gfx950: one workgroup per sample, everything on
 // the device (the reference does B SciPy calls on the host plus six .item() syncs per step,
-// utils/loss/train_loss.py:112-122,183-187).  All statistics in fp32; reductions are wave shuffles + a 4-wave LDS combine.
+// utils/loss/train_loss.py:112-122,183-187).  All statistics in fp32; reductions are the block reductions of row_kernels.h (wave reduction + a 4-wave LDS combine).
 // The loss kernels have a compile-time LABELS mode for ground-truth scene labels (utils/loss/hvu_train_loss.py:27-128, the HVU recipe): the scene class is
 // nb + scene_target[b] instead of the teacher's argmax, so there is no teacher_stats (batch minimum, argmax, logsumexp) and no KL loop over C.  There 'CE' (:94)
 // and 'KL' against the one-hot target on a [1, C] input (:96-101: 'batchmean' divides by 1, 0 log 0 = 0) are the same number, lse_j - z_j[nb + scene_target],
 // and the class has no scene weight.
 #include "common.h"
+#include "row_kernels.h"      // block_sum / block_max, row_stats
 
 namespace {
 
 enum { LMAXS = 8 };
 
-__device__ __forceinline__ float block_sum(float v, float* sm /*[4]*/) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sm[0] + sm[1] + sm[2] + sm[3];
-}
-__device__ __forceinline__ float block_max(float v, float* sm) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-}
 __device__ __forceinline__ float block_min(float v, float* sm) { return -block_max(-v, sm); }
 
 // argmax with first-occurrence tie-break (torch.argmax semantics on CPU): reduce (value, index) pairs
@@ -41,17 +28,6 @@ __device__ __forceinline__ void block_argmax(float v, int idx, float* smv, int* 
 #pragma unroll
     for (int w = 1; w < 4; ++w)
         if (smv[w] > ov || (smv[w] == ov && smi[w] < oi)) { ov = smv[w]; oi = smi[w]; }
-}
-
-// row softmax statistics of Z[row, 0..C): max and logsumexp
-template <typename T>
-__device__ __forceinline__ void row_stats(const T* z, int C, float* sm, float& mx, float& lse) {
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < C; c += 256) m = fmaxf(m, to_f32(z[c]));
-    mx = block_max(m, sm);
-    float s = 0.f;
-    for (int c = threadIdx.x; c < C; c += 256) s += expf(to_f32(z[c]) - mx);
-    lse = mx + logf(block_sum(s, sm));
 }
 
 struct TeacherStats { float pad, lse; int argmax; };

@@ -6,8 +6,8 @@
 //                          row of the clip; CLS: in row 0, zeros elsewhere)
 //
 // What it is bound by: the two streams.  The forward reads h once (77 MB at B = 32, Nt = 1568, D = 768 in bf16), the backward writes dx once; everything between is
-// [B, D] or [B, C].  So two streaming kernels with 16 bytes per lane and access, and around them one-workgroup-per-clip kernels in the manner of fusion_head.hip
-// (strided scalar accesses, two-pass fp32 statistics) plus the library's GEMM / weight-gradient / column-sum launchers.
+// [B, D] or [B, C].  So two streaming kernels with 16 bytes per lane and access, and around them one-workgroup-per-clip kernels built from row_kernels.h as
+// fusion_head.hip's are (strided scalar accesses, two-pass fp32 statistics) plus the library's GEMM / weight-gradient / column-sum launchers (region_host.h).
 //
 //   pool_partial_kernel   one workgroup per (clip, chunk of DEVIAS_POOL_HEAD_CHUNK tokens): lane (r, c) owns the 16-byte column group c and adds rows r, r + R, ... of
 //                         the chunk in that order in fp32 (four loads in flight), the R row sets are combined through LDS in index order, the chunk's sum goes to the
@@ -22,7 +22,8 @@
 #include <string.h>
 #include <atomic>
 #include "roctx_shim.h"
-#include "region_host.h"
+#include "region_host.h"      // split policies, GEMM / weight-gradient calls, the arena carver, argument checks, dispatch_t
+#include "row_kernels.h"       // the per-clip kernels: NT, EPT, block reductions, the row LayerNorm's statistics and backward means
 
 static std::atomic<int64_t> g_pool_head_calls;
 void devias_pool_head_counter_reset() { g_pool_head_calls.store(0, std::memory_order_relaxed); }      // api.hip: devias_counters_reset
@@ -30,7 +31,7 @@ extern "C" int64_t devias_pool_head_launches(void) { return g_pool_head_calls.lo
 
 namespace {
 
-enum { NT = 256, EPT = 4, TOK = DEVIAS_POOL_HEAD_CHUNK, NTS = 384 };      // per-clip kernels: threads, elements per thread (D <= 1024); streaming kernels: tokens per workgroup, most threads
+enum { TOK = DEVIAS_POOL_HEAD_CHUNK, NTS = 384 };      // streaming kernels: tokens per workgroup, most threads
 
 template <typename T> struct Vec16;
 template <> struct Vec16<bf16> { typedef bf16x8 type; enum { N = 8 }; };
@@ -38,16 +39,6 @@ template <> struct Vec16<float> { typedef f32x4 type; enum { N = 4 }; };
 
 // rows of a chunk that the streaming kernels work on side by side: R * (D / VEC) threads, 256 or 384
 inline int stream_rows(int D, int dtype) { const int vc = D / (dtype == DEVIAS_BF16 ? 8 : 4); return NTS / vc; }
-
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* sm /*[8]*/) {
-    a = wave_sum(a); b = wave_sum(b);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = a; sm[4 + (threadIdx.x >> 6)] = b; }
-    __syncthreads();
-    a = sm[0] + sm[1] + sm[2] + sm[3];
-    b = sm[4] + sm[5] + sm[6] + sm[7];
-}
-__device__ __forceinline__ float block_sum(float v, float* sm /*[8]*/) { float z = 0.f; block_sum2(v, z, sm); return v; }
 
 // ---- forward, stage 1: the chunk sums ---------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -104,7 +95,7 @@ __global__ __launch_bounds__(NT) void pool_ln_fwd_kernel(const T* __restrict__ h
                                                          T* __restrict__ a, float* __restrict__ xhat, float* __restrict__ rstd_out) {
     __shared__ float sm[8];
     const int b = blockIdx.x;
-    float v[EPT], q = 0.f;
+    float v[EPT], mean, rstd;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int k = threadIdx.x + NT * i;
@@ -118,13 +109,8 @@ __global__ __launch_bounds__(NT) void pool_ln_fwd_kernel(const T* __restrict__ h
                 v[i] = s * inv_nt;
             }
         }
-        q += v[i];
     }
-    const float mean = block_sum(q, sm) / (float)D;
-    q = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) { const int k = threadIdx.x + NT * i; const float d = k < D ? v[i] - mean : 0.f; q += d * d; }
-    const float rstd = rsqrtf(block_sum(q, sm) / (float)D + eps);
+    row_ln_stats(v, D, eps, sm, mean, rstd);
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int k = threadIdx.x + NT * i;
@@ -165,12 +151,11 @@ __global__ __launch_bounds__(NT) void pool_ln_bwd_kernel(const float* __restrict
             c1 += gy[i]; c2 += gy[i] * xh[i];
         }
     }
-    block_sum2(c1, c2, sm);
-    c1 /= (float)D; c2 /= (float)D;
+    row_ln_bwd_means(c1, c2, D, sm);
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int k = threadIdx.x + NT * i;
-        if (k < D) dxrow[(int64_t)b * D + k] = from_f32<T>(rstd * (gy[i] - c1 - xh[i] * c2) * scale);
+        if (k < D) dxrow[(int64_t)b * D + k] = from_f32<T>(row_ln_dx(gy[i], xh[i], rstd, c1, c2) * scale);
     }
 }
 
@@ -193,46 +178,36 @@ __global__ __launch_bounds__(NTS) void pool_dx_kernel(const T* __restrict__ dxro
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------------------
 inline bool dims_supported(int B, int Nt, int D, int C) {
-    return B >= 1 && Nt >= 1 && (int64_t)B * Nt <= 0x7fffffff && (D == 384 || D == 768 || D == 1024) && C >= 2 && (int64_t)B * 1024 < 0x7fffffff;
+    return B >= 1 && Nt >= 1 && (int64_t)B * Nt <= 0x7fffffff && row_dim_ok(D) && C >= 2 && (int64_t)B * 1024 < 0x7fffffff;
 }
-inline bool dtype_ok(int dtype) { return dtype == DEVIAS_BF16 || dtype == DEVIAS_F32; }
 int64_t kernel_ws_bytes(int B, int D, int C, int dtype) {
     int64_t w = max64(gemm_ws(B, C, D, 0), gemm_ws(B, D, C, 0));
     w = max64(w, max64(wgrad_ws(C, D, B, dtype), devias_colsum_workspace_bytes(B, C)));
     return al256(w) + 256;
 }
-// what lives behind the kernels' workspace: the chunk sums; the forward's x^ / rstd / a where nothing is saved; the backward's temporaries and per-clip partials
-struct Tmp {
-    float *part, *xhat, *rstd, *da, *pg, *pb;
-    char *a, *dxrow;
-    int64_t bytes;
-    Tmp(void* base, int B, int Nt, int D, int dtype) {
-        const int64_t es = esize(dtype), BD = (int64_t)B * D;
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);
-        auto take = [&](int64_t n) { char* q = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return q; };
-        part = (float*)take((int64_t)B * cdiv(Nt, TOK) * D * 4);
-        xhat = (float*)take(BD * 4); rstd = (float*)take((int64_t)B * 4); a = take(BD * es);
-        da = (float*)take(BD * 4); dxrow = take(BD * es); pg = (float*)take(BD * 4); pb = (float*)take(BD * 4);
-        bytes = off;
-    }
-};
+// what backward reads of the forward: the normalised pooled rows and their rstd in fp32, the classifier's input a
 struct Save {
     float *xhat, *rstd; char* a;
+    Save(Arena& ar, int B, int D, int dtype) {
+        xhat = (float*)ar.take((int64_t)B * D * 4); rstd = (float*)ar.take((int64_t)B * 4); a = ar.take((int64_t)B * D * esize(dtype));
+    }
+};
+// what lives behind the kernels' workspace: the chunk sums; a Save of its own, which the forward writes where the caller keeps none; the backward's temporaries and per-clip partials
+struct Tmp {
+    float* part; Save s;          // (carved in this order)
+    float *da, *pg, *pb;
+    char* dxrow;
     int64_t bytes;
-    Save(void* base, int B, int D, int dtype) {
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);
-        auto take = [&](int64_t n) { char* q = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return q; };
-        xhat = (float*)take((int64_t)B * D * 4); rstd = (float*)take((int64_t)B * 4); a = take((int64_t)B * D * esize(dtype));
-        bytes = off;
+    Tmp(Arena ar, int B, int Nt, int D, int dtype) : part((float*)ar.take((int64_t)B * cdiv(Nt, TOK) * D * 4)), s(ar, B, D, dtype) {
+        const int64_t es = esize(dtype), BD = (int64_t)B * D;
+        da = (float*)ar.take(BD * 4); dxrow = ar.take(BD * es); pg = (float*)ar.take(BD * 4); pb = (float*)ar.take(BD * 4);
+        bytes = ar.off;
     }
 };
 
 int pool_check(const devias_pool_head_args* a, const char* who) {
     DEVIAS_REQUIRE(a, "%s: null args", who);
-    DEVIAS_REQUIRE(a->struct_size == (int32_t)sizeof(devias_pool_head_args), "%s: devias_pool_head_args.struct_size is %d, this library's struct has %d bytes (recompile the caller)",
-                   who, a->struct_size, (int)sizeof(devias_pool_head_args));
+    REQUIRE_STRUCT_SIZE(a, devias_pool_head_args, who);
     DEVIAS_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype %d", who, a->dtype);
     DEVIAS_REQUIRE(a->pool == DEVIAS_POOL_MEAN || a->pool == DEVIAS_POOL_CLS, "%s: bad pool %d (DEVIAS_POOL_MEAN or DEVIAS_POOL_CLS)", who, a->pool);
     if (!dims_supported(a->B, a->Nt, a->D, a->C))
@@ -250,11 +225,13 @@ int pool_check(const devias_pool_head_args* a, const char* who) {
 
 extern "C" int64_t devias_pool_head_workspace_bytes(int32_t B, int32_t Nt, int32_t D, int32_t C, int32_t dtype) {
     if (!dims_supported(B, Nt, D, C) || !dtype_ok(dtype)) return 0;
-    return kernel_ws_bytes(B, D, C, dtype) + Tmp(nullptr, B, Nt, D, dtype).bytes;
+    return kernel_ws_bytes(B, D, C, dtype) + Tmp(Arena(nullptr), B, Nt, D, dtype).bytes;
 }
 extern "C" int64_t devias_pool_head_save_bytes(int32_t B, int32_t D, int32_t dtype) {
     if (!dims_supported(B, 1, D, 2) || !dtype_ok(dtype)) return 0;
-    return Save(nullptr, B, D, dtype).bytes;
+    Arena ar(nullptr);
+    Save(ar, B, D, dtype);          // (carved at address 0: the arena ends at its size)
+    return ar.off;
 }
 
 extern "C" int devias_pool_head_fwd(const devias_pool_head_args* a, const void* h, void* token, void* logits, void* save, void* stream) {
@@ -266,26 +243,27 @@ extern "C" int devias_pool_head_fwd(const devias_pool_head_args* a, const void* 
     hipStream_t st = (hipStream_t)stream;
     const int64_t kw = kernel_ws_bytes(B, D, C, a->dtype);
     const Ctx c{a->dtype, a->ws, kw, nullptr, 0, stream};
-    const Tmp t(reinterpret_cast<char*>(a->ws) + kw, B, Nt, D, a->dtype);
-    float *xhat = t.xhat, *rstd = t.rstd; char* av = t.a;
-    if (save) { const Save s(save, B, D, a->dtype); xhat = s.xhat; rstd = s.rstd; av = s.a; }
+    const Tmp t(Arena(reinterpret_cast<char*>(a->ws) + kw), B, Nt, D, a->dtype);
+    Arena own(save);
+    const Save s = save ? Save(own, B, D, a->dtype) : t.s;          // the caller's arena, or (nothing to keep) the one in the workspace
     devias_range rg("pool_head_fwd");
     g_pool_head_calls.fetch_add(1, std::memory_order_relaxed);
     const float inv_nt = 1.0f / (float)Nt;
     if (a->pool == DEVIAS_POOL_MEAN) {
-        if (a->dtype == DEVIAS_BF16) hipLaunchKernelGGL((pool_partial_kernel<bf16>), dim3(B * chunks), dim3(nth), 0, st, (const bf16*)h, Nt, D, chunks, R, t.part);
-        else hipLaunchKernelGGL((pool_partial_kernel<float>), dim3(B * chunks), dim3(nth), 0, st, (const float*)h, Nt, D, chunks, R, t.part);
+        dispatch_t(a->dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((pool_partial_kernel<T>), dim3(B * chunks), dim3(nth), 0, st, (const T*)h, Nt, D, chunks, R, t.part);
+        });
         DEVIAS_CHECK_LAUNCH("devias_pool_head_fwd(partial)");
     }
-    if (a->dtype == DEVIAS_BF16)
-        hipLaunchKernelGGL((pool_ln_fwd_kernel<bf16>), dim3(B), dim3(NT), 0, st, (const bf16*)h, t.part, a->pool, Nt, D, chunks, inv_nt, a->eps, a->ln_w, a->ln_b, a->drop_mask,
-                           (bf16*)token, (bf16*)av, xhat, rstd);
-    else
-        hipLaunchKernelGGL((pool_ln_fwd_kernel<float>), dim3(B), dim3(NT), 0, st, (const float*)h, t.part, a->pool, Nt, D, chunks, inv_nt, a->eps, a->ln_w, a->ln_b, a->drop_mask,
-                           (float*)token, (float*)av, xhat, rstd);
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((pool_ln_fwd_kernel<T>), dim3(B), dim3(NT), 0, st, (const T*)h, t.part, a->pool, Nt, D, chunks, inv_nt, a->eps, a->ln_w, a->ln_b, a->drop_mask,
+                           (T*)token, (T*)s.a, s.xhat, s.rstd);
+    });
     DEVIAS_CHECK_LAUNCH("devias_pool_head_fwd(layernorm)");
     Epi e; e.bias = a->bias;
-    RUN(gemm(c, av, a->W, logits, B, C, D, D, D, 0, 0, e));
+    RUN(gemm(c, s.a, a->W, logits, B, C, D, D, D, 0, 0, e));
     return DEVIAS_OK;
 }
 
@@ -294,15 +272,15 @@ extern "C" int devias_pool_head_bwd(const devias_pool_head_args* a, const void* 
     const char* who = "devias_pool_head_bwd";
     RUN(pool_check(a, who));
     DEVIAS_REQUIRE(save && dlogits && dx && g && aligned16(save) && aligned16(dx), "%s: null pointer (save / dlogits / dx / grads), or save / dx not 16-byte aligned", who);
-    DEVIAS_REQUIRE(g->struct_size == (int32_t)sizeof(devias_pool_head_grads), "%s: devias_pool_head_grads.struct_size is %d, this library's struct has %d bytes (recompile the caller)",
-                   who, g->struct_size, (int)sizeof(devias_pool_head_grads));
+    REQUIRE_STRUCT_SIZE(g, devias_pool_head_grads, who);
     DEVIAS_REQUIRE(g->dW && g->db && g->dln_w && g->dln_b, "%s: null gradient destination", who);
     const int B = a->B, Nt = a->Nt, D = a->D, C = a->C, chunks = cdiv(Nt, TOK), R = stream_rows(D, a->dtype), nth = R * (D / (a->dtype == DEVIAS_BF16 ? 8 : 4));
     hipStream_t st = (hipStream_t)stream;
     const int64_t kw = kernel_ws_bytes(B, D, C, a->dtype);
     const Ctx c{a->dtype, a->ws, kw, nullptr, 0, stream};
-    const Tmp t(reinterpret_cast<char*>(a->ws) + kw, B, Nt, D, a->dtype);
-    const Save s(const_cast<void*>(save), B, D, a->dtype);
+    const Tmp t(Arena(reinterpret_cast<char*>(a->ws) + kw), B, Nt, D, a->dtype);
+    Arena own(save);
+    const Save s(own, B, D, a->dtype);
     devias_range rg("pool_head_bwd");
     g_pool_head_calls.fetch_add(1, std::memory_order_relaxed);
     // classifier
@@ -312,15 +290,15 @@ extern "C" int devias_pool_head_bwd(const devias_pool_head_args* a, const void* 
     RUN(gemm(c, dlogits, a->W, t.da, B, D, C, C, D, 0, 1, e, 1 /* fp32 output: da is not rounded to T */));
     // LayerNorm backward per clip, then every row of dx
     const float scale = a->pool == DEVIAS_POOL_MEAN ? 1.0f / (float)Nt : 1.0f;
-    if (a->dtype == DEVIAS_BF16) {
-        hipLaunchKernelGGL((pool_ln_bwd_kernel<bf16>), dim3(B), dim3(NT), 0, st, t.da, (const bf16*)dtoken, a->drop_mask, s.xhat, s.rstd, a->ln_w, D, scale, (bf16*)t.dxrow, t.pg, t.pb);
-        DEVIAS_CHECK_LAUNCH("devias_pool_head_bwd(layernorm)");
-        hipLaunchKernelGGL((pool_dx_kernel<bf16>), dim3(B * chunks), dim3(nth), 0, st, (const bf16*)t.dxrow, a->pool, Nt, D, chunks, R, (bf16*)dx);
-    } else {
-        hipLaunchKernelGGL((pool_ln_bwd_kernel<float>), dim3(B), dim3(NT), 0, st, t.da, (const float*)dtoken, a->drop_mask, s.xhat, s.rstd, a->ln_w, D, scale, (float*)t.dxrow, t.pg, t.pb);
-        DEVIAS_CHECK_LAUNCH("devias_pool_head_bwd(layernorm)");
-        hipLaunchKernelGGL((pool_dx_kernel<float>), dim3(B * chunks), dim3(nth), 0, st, (const float*)t.dxrow, a->pool, Nt, D, chunks, R, (float*)dx);
-    }
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((pool_ln_bwd_kernel<T>), dim3(B), dim3(NT), 0, st, t.da, (const T*)dtoken, a->drop_mask, s.xhat, s.rstd, a->ln_w, D, scale, (T*)t.dxrow, t.pg, t.pb);
+    });
+    DEVIAS_CHECK_LAUNCH("devias_pool_head_bwd(layernorm)");
+    dispatch_t(a->dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((pool_dx_kernel<T>), dim3(B * chunks), dim3(nth), 0, st, (const T*)t.dxrow, a->pool, Nt, D, chunks, R, (T*)dx);
+    });
     DEVIAS_CHECK_LAUNCH("devias_pool_head_bwd(dx)");
     // d gamma / d beta: per-clip partials summed over the clips in index order, ONE launch
     DeviasDeferList dl; dl.n = 0;

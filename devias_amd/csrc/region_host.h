@@ -1,5 +1,6 @@
-// Host-side helpers shared by the fused-region units (regions.hip, fusion_head.hip): the Python host's automatic split-K choices restated, and the GEMM / weight-gradient /
-// LayerNorm / column-sum calls a region makes with them.  Every unit that includes this file gets its own copy (anonymous namespace); devias_policy_* (regions.hip) export the policies.
+// Host-side helpers shared by the fused-region units (regions.hip, fusion_head.hip, pool_head.hip): the entry points' argument checks and dtype dispatch, the arena carver,
+// the Python host's automatic split-K choices restated, and the GEMM / weight-gradient / LayerNorm / column-sum calls a region makes with them.  Every unit that includes
+// this file gets its own copy (anonymous namespace); devias_policy_* (regions.hip) export the policies.  The device side of the head units' row kernels: row_kernels.h.
 #pragma once
 #include "common.h"
 #include <stdlib.h>
@@ -9,6 +10,27 @@ namespace {
 
 inline int64_t al256(int64_t n) { return (n + 255) & ~(int64_t)255; }
 inline int esize(int dtype) { return dtype == DEVIAS_BF16 ? 2 : 4; }
+
+// ---- argument checks and the dtype dispatch of the entry points ------------------------------------------------------------------------------------------
+inline bool dtype_ok(int dtype) { return dtype == DEVIAS_BF16 || dtype == DEVIAS_F32; }
+inline bool row_dim_ok(int D) { return D == 384 || D == 768 || D == 1024; }      // what the one-workgroup-per-row kernels of the head regions hold in registers
+// a struct that carries its own size: a caller compiled against another version of the header is refused
+#define REQUIRE_STRUCT_SIZE(p, type, who)                                                                                                               \
+    DEVIAS_REQUIRE((p)->struct_size == (int32_t)sizeof(type), "%s: " #type ".struct_size is %d, this library's struct has %d bytes (recompile the caller)", who, \
+                   (p)->struct_size, (int)sizeof(type))
+// f(TypeTag<bf16>{}) or f(TypeTag<float>{}) for a dtype that dtype_ok accepted; inside the generic lambda: using T = typename decltype(tag)::type
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F> inline void dispatch_t(int dtype, F&& f) {
+    if (dtype == DEVIAS_BF16) f(TypeTag<bf16>{}); else f(TypeTag<float>{});
+}
+
+// ---- the arena carver: consecutive pieces of a caller-owned buffer, each starting on a 256-byte step ------------------------------------------------------
+// Integer arithmetic: the size queries lay the arena out at address 0 (base = nullptr) and read `off`.
+struct Arena {
+    uintptr_t base; int64_t off = 0;
+    explicit Arena(const void* p) : base(reinterpret_cast<uintptr_t>(p)) {}
+    char* take(int64_t bytes) { char* q = reinterpret_cast<char*>(base + (uintptr_t)off); off += al256(bytes); return q; }
+};
 
 // ---- the split policies of the Python host (devias_amd/ops.py: gemm / wgrad / auto_split_k), restated; tests/test_regions_cpu.py keeps them equal ----
 int small_m_split(int M, int N, int K, int trans_a) {

@@ -25,14 +25,12 @@ struct BlockSave {
     int64_t bytes;
     BlockSave(void* base, int B, int N, int D, int H, int hid, int dtype) {
         const int64_t M = (int64_t)B * N, es = esize(dtype);
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
-        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
-        u = take(M * D * es); qkv = take(M * 3 * D * es); o = take(M * D * es); x1 = take(M * D * es); u2 = take(M * D * es);
-        hpre = take(M * hid * es); hact = take(M * hid * es);
-        mean1 = (float*)take(M * 4); rstd1 = (float*)take(M * 4); mean2 = (float*)take(M * 4); rstd2 = (float*)take(M * 4);
-        lse = (float*)take((int64_t)B * H * N * 4);
-        bytes = off;
+        Arena ar(base);
+        u = ar.take(M * D * es); qkv = ar.take(M * 3 * D * es); o = ar.take(M * D * es); x1 = ar.take(M * D * es); u2 = ar.take(M * D * es);
+        hpre = ar.take(M * hid * es); hact = ar.take(M * hid * es);
+        mean1 = (float*)ar.take(M * 4); rstd1 = (float*)ar.take(M * 4); mean2 = (float*)ar.take(M * 4); rstd2 = (float*)ar.take(M * 4);
+        lse = (float*)ar.take((int64_t)B * H * N * 4);
+        bytes = ar.off;
     }
 };
 struct BlockScratch {
@@ -44,18 +42,16 @@ struct BlockScratch {
     int64_t bytes;
     BlockScratch(void* base, int B, int N, int D, int H, int hid, int dtype) {
         const int64_t M = (int64_t)B * N, es = esize(dtype);
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
-        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
-        big = take(M * (hid > 3 * D ? hid : 3 * D) * es); small = take(M * D * es); dx1 = take(M * D * es); g = take(M * D * es);
-        delta = (float*)take((int64_t)B * H * N * 4);
+        Arena ar(base);
+        big = ar.take(M * (hid > 3 * D ? hid : 3 * D) * es); small = ar.take(M * D * es); dx1 = ar.take(M * D * es); g = ar.take(M * D * es);
+        delta = (float*)ar.take((int64_t)B * H * N * 4);
         const int64_t lnw = devias_layernorm_bwd_workspace_bytes((int)M, D), csw = devias_colsum_workspace_bytes((int)M, 3 * D);
-        p_ln2 = (float*)take(lnw); p_ln1 = (float*)take(lnw);
-        p_db1 = (float*)take(max64((int64_t)cdiv(M, 128) * hid * 4, devias_colsum_workspace_bytes((int)M, hid)));
-        p_b2 = (float*)take(csw); p_bp = (float*)take(csw);
+        p_ln2 = (float*)ar.take(lnw); p_ln1 = (float*)ar.take(lnw);
+        p_db1 = (float*)ar.take(max64((int64_t)cdiv(M, 128) * hid * 4, devias_colsum_workspace_bytes((int)M, hid)));
+        p_b2 = (float*)ar.take(csw); p_bp = (float*)ar.take(csw);
         const int64_t abw = max64(csw, devias_mhsa_bwd_bias_workspace_bytes(B, N, H));
-        p_q = (float*)take(abw); p_v = (float*)take(abw);
-        bytes = off;
+        p_q = (float*)ar.take(abw); p_v = (float*)ar.take(abw);
+        bytes = ar.off;
     }
 };
 // forward ran the qkv GEMM on the caller's q-scaled copies (ABI 167): bf16, both pointers given
@@ -69,16 +65,14 @@ struct BlockInferWs {
     int64_t kws_bytes, bytes;
     BlockInferWs(void* base, int B, int N, int64_t rows, int D, int H, int hid, int dtype) {
         const int64_t es = esize(dtype);
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
-        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
-        u = take(rows * D * es); qkv = take(rows * 3 * D * es); o = take(rows * D * es); x1 = take(rows * D * es); hact = take(rows * hid * es);
-        mean = (float*)take(rows * 4); rstd = (float*)take(rows * 4);
-        lse = (float*)take((int64_t)B * H * N * 4);
+        Arena ar(base);
+        u = ar.take(rows * D * es); qkv = ar.take(rows * 3 * D * es); o = ar.take(rows * D * es); x1 = ar.take(rows * D * es); hact = ar.take(rows * hid * es);
+        mean = (float*)ar.take(rows * 4); rstd = (float*)ar.take(rows * 4);
+        lse = (float*)ar.take((int64_t)B * H * N * 4);
         const int M = (int)rows;
         kws_bytes = al256(max64(max64(gemm_ws(M, 3 * D, D, 0), gemm_ws(M, D, D, 0)), max64(gemm_ws(M, hid, D, 0), gemm_ws(M, D, hid, 0)))) + 256;
-        kws = (float*)take(kws_bytes);
-        bytes = off;
+        kws = (float*)ar.take(kws_bytes);
+        bytes = ar.off;
     }
 };
 inline bool infer_dims_ok(int32_t B, int32_t N, int64_t rows, int32_t D, int32_t H, int32_t hid) {
@@ -88,7 +82,7 @@ int block_check(const devias_block_args* a, const char* who, bool need_save = tr
     DEVIAS_REQUIRE(a, "%s: null args", who);
     DEVIAS_REQUIRE(a->B > 0 && a->N > 0 && a->D > 0 && a->H > 0 && a->hidden > 0 && a->D == a->H * 64, "%s: bad dims (B=%d N=%d D=%d H=%d hidden=%d; head dim must be 64)", who,
                    a->B, a->N, a->D, a->H, a->hidden);
-    DEVIAS_REQUIRE(a->dtype == DEVIAS_BF16 || a->dtype == DEVIAS_F32, "%s: bad dtype %d", who, a->dtype);
+    DEVIAS_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype %d", who, a->dtype);
     DEVIAS_REQUIRE(a->n1w && a->n1b && a->n2w && a->n2b && a->Wqkv && a->Wp && a->W1 && a->W2 && a->qkv_bias && a->pb && a->b1 && a->b2, "%s: null parameter", who);
     DEVIAS_REQUIRE((a->WqkvS != nullptr) == (a->qkv_biasS != nullptr) && (!a->WqkvS || a->dtype == DEVIAS_BF16), "%s: WqkvS and qkv_biasS go together (bf16 only)", who);
     if (!need_save) {          // the forward-only block: no arena, and a workspace of its own size (checked by the caller, which knows `rows`)
@@ -270,11 +264,9 @@ struct HeadSave {
     int64_t bytes;
     HeadSave(void* base, int R, int D, int h1, int h2, int dtype) {
         const int64_t es = esize(dtype);
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
-        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
-        m1 = take((int64_t)R * h1 * es); m2 = take((int64_t)R * h2 * es); sd = take((int64_t)R * D * es);
-        bytes = off;
+        Arena ar(base);
+        m1 = ar.take((int64_t)R * h1 * es); m2 = ar.take((int64_t)R * h2 * es); sd = ar.take((int64_t)R * D * es);
+        bytes = ar.off;
     }
 };
 int64_t head_tmp_bytes(int R, int D, int h1, int h2, int G, int dtype) {       // dp3 [R,G], dp2 [R,h2], dp1 [R,h1], ds_m [R,D], d(dropped slots) [R,D]
@@ -283,7 +275,7 @@ int64_t head_tmp_bytes(int R, int D, int h1, int h2, int G, int dtype) {       /
 }
 int head_check(const devias_head_args* a, const char* who) {
     DEVIAS_REQUIRE(a && a->R > 0 && a->D > 0 && a->C > 0 && a->h1 > 0 && a->h2 > 0 && a->G > 0, "%s: bad dims", who);
-    DEVIAS_REQUIRE(a->dtype == DEVIAS_BF16 || a->dtype == DEVIAS_F32, "%s: bad dtype %d", who, a->dtype);
+    DEVIAS_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype %d", who, a->dtype);
     DEVIAS_REQUIRE(a->Wh && a->bh && a->W0 && a->b0 && a->W2 && a->b2 && a->W4 && a->b4 && a->ws, "%s: null parameter / workspace", who);
     DEVIAS_REQUIRE(a->ws_bytes >= devias_head_workspace_bytes(a->R, a->D, a->C, a->h1, a->h2, a->G, a->dtype), "%s: workspace too small", who);
     return DEVIAS_OK;
@@ -369,20 +361,18 @@ struct AggSave {
     AggSave(void* base, const devias_agg_args* a) {
         const int64_t es = esize(a->dtype), M = (int64_t)a->B * a->N, R = (int64_t)a->B * a->S, D = a->D, hD = (int64_t)a->heads * a->D, F = a->ff;
         const int nset = a->tied ? 1 : a->depth;
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
-        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
-        feats = take(M * D * es); m0 = (float*)take(M * 4); r0 = (float*)take(M * 4);
+        Arena ar(base);
+        feats = ar.take(M * D * es); m0 = (float*)ar.take(M * 4); r0 = (float*)ar.take(M * 4);
         for (int i = 0; i < nset; ++i) {
-            c[i] = take(M * D * es); mc[i] = (float*)take(M * 4); rc[i] = (float*)take(M * 4);
-            Wqk[i] = take(hD * D * es); Wov[i] = take(D * hD * es);
+            c[i] = ar.take(M * D * es); mc[i] = (float*)ar.take(M * 4); rc[i] = (float*)ar.take(M * 4);
+            Wqk[i] = ar.take(hD * D * es); Wov[i] = ar.take(D * hD * es);
         }
         // per-layer tensors, one stack per field, the layers contiguous: the deferred weight gradients of a tied weight set reduce over all its
         // layers' rows in ONE product ([depth * R, .] operands)
         {
-            char *xs_in = take(a->depth * R * D * es), *qn = take(a->depth * R * D * es), *z = take(a->depth * R * hD * es), *xs1 = take(a->depth * R * D * es);
-            char *f = take(a->depth * R * D * es), *fpre = take(a->depth * R * F * es), *fact = take(a->depth * R * F * es);
-            float *mq = (float*)take(a->depth * R * 4), *rq = (float*)take(a->depth * R * 4), *mf = (float*)take(a->depth * R * 4), *rf = (float*)take(a->depth * R * 4);
+            char *xs_in = ar.take(a->depth * R * D * es), *qn = ar.take(a->depth * R * D * es), *z = ar.take(a->depth * R * hD * es), *xs1 = ar.take(a->depth * R * D * es);
+            char *f = ar.take(a->depth * R * D * es), *fpre = ar.take(a->depth * R * F * es), *fact = ar.take(a->depth * R * F * es);
+            float *mq = (float*)ar.take(a->depth * R * 4), *rq = (float*)ar.take(a->depth * R * 4), *mf = (float*)ar.take(a->depth * R * 4), *rf = (float*)ar.take(a->depth * R * 4);
             for (int l = 0; l < a->depth; ++l) {
                 Layer& y = L[l];
                 y.xs_in = xs_in + l * R * D * es; y.qn = qn + l * R * D * es; y.z = z + l * R * hD * es; y.xs1 = xs1 + l * R * D * es; y.f = f + l * R * D * es;
@@ -391,11 +381,11 @@ struct AggSave {
             }
         }
         qp_layer = R * hD * es; attn_layer = (int64_t)a->B * a->heads * a->S * a->N * 4; rsum_layer = (int64_t)a->B * a->heads * a->S * 4;
-        qp_stack = take(qp_layer * a->depth);
-        attn_stack = (float*)take(attn_layer * a->depth);
-        rsum_stack = (float*)take(rsum_layer * a->depth);
-        xs_last = take(R * D * es); ml = (float*)take(R * 4); rl = (float*)take(R * 4);
-        bytes = off;
+        qp_stack = ar.take(qp_layer * a->depth);
+        attn_stack = (float*)ar.take(attn_layer * a->depth);
+        rsum_stack = (float*)ar.take(rsum_layer * a->depth);
+        xs_last = ar.take(R * D * es); ml = (float*)ar.take(R * 4); rl = (float*)ar.take(R * 4);
+        bytes = ar.off;
     }
 };
 struct AggScratch {
@@ -415,22 +405,20 @@ struct AggScratch {
         const int nset = a->tied ? 1 : a->depth;
         const int nl = a->tied ? a->depth : 1;
         const int64_t K = 2 * (int64_t)nl * a->heads * a->S, Np = (a->N + 7) / 8 * 8;
-        int64_t off = 0;
-        const uintptr_t p = reinterpret_cast<uintptr_t>(base);          // (integer arithmetic: the size queries lay the arena out at address 0)
-        auto take = [&](int64_t n) { char* r = reinterpret_cast<char*>(p + (uintptr_t)off); off += al256(n); return r; };
+        Arena ar(base);
         dz_layer = R * hD * es; ds_layer = (int64_t)a->B * a->heads * a->S * a->N * 4;
-        dz_stack = take(dz_layer * a->depth); ds_stack = (float*)take(ds_layer * a->depth);
+        dz_stack = ar.take(dz_layer * a->depth); ds_stack = (float*)ar.take(ds_layer * a->depth);
         rd = R * D * es; rf = R * F * es; rh = R * hD * es;
-        dxs_stack = take((a->depth + 1) * rd);         // slot l + 1 = gradient of layer l's output; slot 0 = gradient of the latents' rows
-        dfpre_stack = take(a->depth * rf); dxs1_stack = take(a->depth * rd); dqp_stack = take(a->depth * rh);
-        df = take(rd); dqn = take(rd);
-        coef = take((int64_t)a->B * K * Np * es); vec = take((int64_t)a->B * K * D * es); dc = take(M * D * es);
-        dfeats[0] = take(M * D * es); dfeats[1] = take(M * D * es);
-        for (int i = 0; i < nset; ++i) { gWqk[i] = (float*)take(hD * D * 4); gWov[i] = (float*)take(D * hD * 4); }
-        gqk_t = take(hD * D * es); gov_t = take(D * hD * es);
+        dxs_stack = ar.take((a->depth + 1) * rd);         // slot l + 1 = gradient of layer l's output; slot 0 = gradient of the latents' rows
+        dfpre_stack = ar.take(a->depth * rf); dxs1_stack = ar.take(a->depth * rd); dqp_stack = ar.take(a->depth * rh);
+        df = ar.take(rd); dqn = ar.take(rd);
+        coef = ar.take((int64_t)a->B * K * Np * es); vec = ar.take((int64_t)a->B * K * D * es); dc = ar.take(M * D * es);
+        dfeats[0] = ar.take(M * D * es); dfeats[1] = ar.take(M * D * es);
+        for (int i = 0; i < nset; ++i) { gWqk[i] = (float*)ar.take(hD * D * 4); gWov[i] = (float*)ar.take(D * hD * 4); }
+        gqk_t = ar.take(hD * D * es); gov_t = ar.take(D * hD * es);
         lnp_layer = devias_layernorm_bwd_parts_count((int)R) * 3 * D;
-        for (int i = 0; i < nset; ++i) { lnp_ffn[i] = (float*)take(nl * lnp_layer * 4); lnp_q[i] = (float*)take(nl * lnp_layer * 4); }
-        bytes = off;
+        for (int i = 0; i < nset; ++i) { lnp_ffn[i] = (float*)ar.take(nl * lnp_layer * 4); lnp_q[i] = (float*)ar.take(nl * lnp_layer * 4); }
+        bytes = ar.off;
     }
 };
 int agg_check(const devias_agg_args* a, const char* who) {
@@ -438,7 +426,7 @@ int agg_check(const devias_agg_args* a, const char* who) {
     DEVIAS_REQUIRE(a->B > 0 && a->N > 0 && a->S >= 1 && a->S <= 4 && a->depth >= 1 && a->depth <= DEVIAS_AGG_MAX_DEPTH && a->heads > 0 && a->dh > 0 && a->ff > 0,
                    "%s: bad dims (S <= 4, depth <= %d)", who, DEVIAS_AGG_MAX_DEPTH);
     DEVIAS_REQUIRE(a->D == 384 || a->D == 512 || a->D == 768 || a->D == 1024, "%s: context dim must be 384, 512, 768 or 1024, got %d", who, a->D);
-    DEVIAS_REQUIRE(a->dtype == DEVIAS_BF16 || a->dtype == DEVIAS_F32, "%s: bad dtype %d", who, a->dtype);
+    DEVIAS_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype %d", who, a->dtype);
     DEVIAS_REQUIRE(a->norm_w && a->norm_b && a->latents && a->last_w && a->last_b && a->ws && a->save, "%s: null pointer", who);
     const int nset = a->tied ? 1 : a->depth;
     for (int i = 0; i < nset; ++i) {

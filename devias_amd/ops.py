@@ -53,6 +53,13 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return ws
 
 
+def attach_workspace(a, nbytes: int, device) -> None:
+    """point an argument struct's ws / ws_bytes at the stream's workspace of at least `nbytes`.  A backward passes a.ws_bytes: the stream's workspace may have been
+    re-allocated larger since the struct was filled"""
+    ws = workspace(nbytes, device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+
+
 def get_option(name: str) -> int:
     """devias_get_option: the current value of a process-wide option (to restore it after a temporary change)"""
     v = ctypes.c_int32(0)
@@ -135,8 +142,7 @@ def pool_head_args(B: int, Nt: int, pool: int, eps: float, W: torch.Tensor, bias
     nws = lib.devias_pool_head_workspace_bytes(B, Nt, D, C, dt)
     if nws <= 0:
         raise NotImplementedError(f"devias_pool_head: unsupported dims B={B} Nt={Nt} D={D} C={C} (D in 384 / 768 / 1024, B, Nt >= 1, C >= 2)")
-    ws = workspace(nws, W.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    attach_workspace(a, nws, W.device)
     return a
 
 
@@ -145,8 +151,7 @@ def pool_head_fwd(a: "_lib.PoolHeadArgs", h: torch.Tensor, save: bool = True):
     lib = _lib.load()
     _chk(h, "pool_head.h")
     assert tuple(h.shape) == (a.B * a.Nt, a.D) and dt_code(h.dtype) == a.dtype
-    ws = workspace(a.ws_bytes, h.device)                  # (the stream's workspace may have been re-allocated larger since the struct was filled)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    attach_workspace(a, a.ws_bytes, h.device)
     arena = torch.empty((lib.devias_pool_head_save_bytes(a.B, a.D, a.dtype),), dtype=torch.uint8, device=h.device) if save else None
     token = torch.empty((a.B, a.D), dtype=h.dtype, device=h.device)
     logits = torch.empty((a.B, a.C), dtype=h.dtype, device=h.device)
@@ -168,8 +173,7 @@ def pool_head_bwd(a: "_lib.PoolHeadArgs", arena: torch.Tensor, dlogits: torch.Te
         _chk(t, "pool_head.grad", torch.float32)
         assert tuple(t.shape) == shape
     g.dW, g.db, g.dln_w, g.dln_b = [t.data_ptr() for t in grads]
-    ws = workspace(a.ws_bytes, dx.device)
-    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    attach_workspace(a, a.ws_bytes, dx.device)
     _lib.check(lib.devias_pool_head_bwd(ctypes.byref(a), arena.data_ptr(), dlogits.data_ptr(), _p(dtoken), dx.data_ptr(), ctypes.byref(g), _stream()),
                "devias_pool_head_bwd")
 

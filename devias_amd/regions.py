@@ -57,16 +57,25 @@ class _GradDest:
         return [t.data_ptr() for t in self.out]
 
 
-def _region_state(ctx, who: str, x: torch.Tensor):
+def _region_state(ctx, who: str, index: int):
     """The fused-region Functions keep their arena, weight copies and argument struct on `ctx` as raw pointers (not save_for_backward: the arena is
     written by the library, not by autograd) and drop them after ONE backward.  A second backward (retain_graph=True) or an input modified in place
-    between forward and backward must fail with a message, not with a TypeError on None or silently wrong gradients."""
+    between forward and backward must fail with a message, not with a TypeError on None or silently wrong gradients.  `index`: where the
+    region's input stands in ctx.keep."""
     if ctx.keep is None:
         raise RuntimeError(f"{who}: backward already consumed this region's saved arena; the fused regions support ONE backward per forward "
                            "(run forward again instead of retain_graph=True)")
+    x = ctx.keep[index]
     if x._version != ctx.x_version:
         raise RuntimeError(f"{who}: the region's input was modified in place between forward and backward (version {ctx.x_version} -> {x._version}); "
                            "its saved activations no longer match it")
+
+
+def _will_backward(ctx, grad_enabled) -> bool:
+    """Whether a forward has to save for a backward: the caller had autograd on (read BEFORE apply: inside forward it is always off) and an input requires a
+    gradient.  Where not, nothing is kept on `ctx` and the caller hands the library no arena (save = NULL: it keeps the intermediates in its workspace; same bits)."""
+    ctx.keep = ctx.args = None
+    return bool(grad_enabled) and any(ctx.needs_input_grad)
 
 
 class EncoderBlockRegionFn(Function):
@@ -84,7 +93,6 @@ class EncoderBlockRegionFn(Function):
         keep = [_f32(n1w), _f32(n1b), _f32(n2w), _f32(n2b)] + [_WCACHE.get(w, cdt) for w in (qkvw, pw, f1w, f2w)] + \
                [_WCACHE.qkv_bias(qb, vb), _f32(pb), _f32(f1b), _f32(f2b)]
         save = torch.empty((lib.devias_encoder_block_save_bytes(B, N, D, H, hid, dt),), dtype=torch.uint8, device=dev)
-        ws = ops.workspace(lib.devias_encoder_block_workspace_bytes(B, N, D, H, hid, dt), dev)
         a = _L.BlockArgs()
         a.B, a.N, a.D, a.H, a.hidden, a.dtype, a.eps = B, N, D, H, hid, dt, eps
         (a.n1w, a.n1b, a.n2w, a.n2b, a.Wqkv, a.Wp, a.W1, a.W2, a.qkv_bias, a.pb, a.b1, a.b2) = [t.data_ptr() for t in keep]
@@ -99,7 +107,8 @@ class EncoderBlockRegionFn(Function):
             (a.WqkvT, a.WpT, a.W1T, a.W2T) = [t.data_ptr() for t in wt]
         a.ds1 = ds1.data_ptr() if ds1 is not None else None
         a.ds2 = ds2.data_ptr() if ds2 is not None else None
-        a.save, a.ws, a.ws_bytes = save.data_ptr(), ws.data_ptr(), ws.numel() * 4
+        a.save = save.data_ptr()
+        ops.attach_workspace(a, lib.devias_encoder_block_workspace_bytes(B, N, D, H, hid, dt), dev)
         x2 = torch.empty_like(x)
         _L.check(lib.devias_encoder_block_fwd(_ct.byref(a), x.data_ptr(), x2.data_ptr(), ops._stream()), "devias_encoder_block_fwd")
         ctx.args = a
@@ -113,7 +122,7 @@ class EncoderBlockRegionFn(Function):
     def backward(ctx, dx2):
         B, N, H, eps, cdt = ctx.meta
         lib = _L.load()
-        _region_state(ctx, "EncoderBlockRegionFn", ctx.keep[4] if ctx.keep is not None else None)
+        _region_state(ctx, "EncoderBlockRegionFn", 4)
         a = ctx.args
         keep, save, ds1, ds2, x = ctx.keep
         (p_n1w, p_n1b, p_qkvw, p_pw, p_pb, p_n2w, p_n2b, p_f1w, p_f1b, p_f2w, p_f2b, p_qb, p_vb) = ctx.params
@@ -130,8 +139,7 @@ class EncoderBlockRegionFn(Function):
         g = _L.BlockGrads()
         (g.dn1w, g.dn1b, g.dWqkv, g.dbq, g.dWp, g.dbp, g.dn2w, g.dn2b, g.dW1, g.db1, g.dW2, g.db2, g.dx_colsum, g.dbv) = gd.ptrs()
         g.db2_done = 1 if ready is not None else 0
-        ws = ops.workspace(a.ws_bytes, dev)                 # (the stream's workspace may have been re-allocated larger since forward)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        ops.attach_workspace(a, a.ws_bytes, dev)
         nscr = lib.devias_encoder_block_scratch_bytes(B, N, D, H, hid, a.dtype)
         scr = _scratch(nscr, dev)
         dx = torch.empty_like(x)
@@ -178,11 +186,10 @@ class HeadRegionFn(Function):
         C, h1, h2, G = hw.shape[0], w0.shape[0], w2.shape[0], w4.shape[0]
         dt = ops.dt_code(cdt)
         keep = [_WCACHE.get(w, cdt) for w in (hw, w0, w2, w4)] + [_f32(hb), _f32(b0), _f32(b2), _f32(b4)]
-        ws = ops.workspace(lib.devias_head_workspace_bytes(R, D, C, h1, h2, G, dt), dev)
         a = _L.HeadArgs()
         a.R, a.D, a.C, a.h1, a.h2, a.G, a.dtype = R, D, C, h1, h2, G, dt
         (a.Wh, a.W0, a.W2, a.W4, a.bh, a.b0, a.b2, a.b4) = [t.data_ptr() for t in keep]
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        ops.attach_workspace(a, lib.devias_head_workspace_bytes(R, D, C, h1, h2, G, dt), dev)
         if drop_mask is not None:            # fc_dropout (modeling_slot.py:291,393): 0 / (1/keep) per element of the head's input
             drop_mask = ops._chk(drop_mask, "head.drop_mask", torch.float32)
             assert drop_mask.shape == (R, D)
@@ -200,7 +207,7 @@ class HeadRegionFn(Function):
     @staticmethod
     def backward(ctx, dZ, dM):
         lib = _L.load()
-        _region_state(ctx, "HeadRegionFn", ctx.keep[2] if ctx.keep is not None else None)
+        _region_state(ctx, "HeadRegionFn", 2)
         a = ctx.args
         keep, save, slots, Mk, drop_mask = ctx.keep
         hw, hb, w0, b0, w2, b2, w4, b4 = ctx.params
@@ -211,8 +218,7 @@ class HeadRegionFn(Function):
                         (w4, tuple(w4.shape)), (b4, tuple(b4.shape))], dev)
         g = _L.HeadGrads()
         (g.dWh, g.dbh, g.dW0, g.db0, g.dW2, g.db2, g.dW4, g.db4) = gd.ptrs()
-        ws = ops.workspace(a.ws_bytes, dev)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        ops.attach_workspace(a, a.ws_bytes, dev)
         dslots = torch.empty_like(slots)
         _L.check(lib.devias_head_bwd(_ct.byref(a), slots.data_ptr(), Mk.data_ptr(), save.data_ptr(), dZ.data_ptr(), dM.data_ptr(), dslots.data_ptr(),
                                      _ct.byref(g), ops._stream()), "devias_head_bwd")
@@ -252,9 +258,8 @@ class FusionHeadFn(Function):
         nws = lib.devias_fusion_head_workspace_bytes(B, S, D, C, Cd, dt)
         if nws <= 0:
             raise NotImplementedError(f"devias_fusion_head: unsupported dims B={B} S={S} D={D} C={C} Cd={Cd} (D in 384 / 768 / 1024, S <= 4, Cd >= 2)")
-        ws = ops.workspace(nws, dev)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
-        need_bwd = bool(grad_enabled) and any(ctx.needs_input_grad)
+        ops.attach_workspace(a, nws, dev)
+        need_bwd = _will_backward(ctx, grad_enabled)
         save = torch.empty((lib.devias_fusion_head_save_bytes(B, D, dt),), dtype=torch.uint8, device=dev) if need_bwd else None
         inp = torch.empty((B, 2 * D), dtype=cdt, device=dev)
         out = torch.empty((B, Cd), dtype=cdt, device=dev)
@@ -267,14 +272,12 @@ class FusionHeadFn(Function):
             ctx.keep = (mats + vecs, save, slots, inp, idx, drop_mask)
             ctx.x_version = slots._version
             ctx.params = (an_w, an_b, sn_w, sn_b, dw, db, lw, lb, iw, ib, cw, cb)
-        else:
-            ctx.keep = ctx.args = None
         return inp, out, idx
 
     @staticmethod
     def backward(ctx, dinp, dout, _didx):
         lib = _L.load()
-        _region_state(ctx, "FusionHeadFn", ctx.keep[2] if ctx.keep is not None else None)
+        _region_state(ctx, "FusionHeadFn", 2)
         a = ctx.args
         keep, save, slots, inp, idx, drop_mask = ctx.keep
         an_w, an_b, sn_w, sn_b, dw, db, lw, lb, iw, ib, cw, cb = ctx.params
@@ -288,8 +291,7 @@ class FusionHeadFn(Function):
         g = _L.FusionGrads()
         g.struct_size = _ct.sizeof(_L.FusionGrads)
         (g.dan_w, g.dan_b, g.dsn_w, g.dsn_b, g.dWd, g.dbd, g.dln_w, g.dln_b, g.din_w, g.din_b, g.dWc, g.dbc) = [(t.data_ptr() if t is not None else None) for t in outs]
-        ws = ops.workspace(a.ws_bytes, dev)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        ops.attach_workspace(a, a.ws_bytes, dev)
         dslots = torch.empty_like(slots)
         _L.check(lib.devias_fusion_head_bwd(_ct.byref(a), slots.data_ptr(), idx.data_ptr(), inp.data_ptr(), save.data_ptr(), dout.data_ptr(),
                                             dinp.data_ptr() if dinp is not None else None, dslots.data_ptr(), _ct.byref(g), ops._stream()), "devias_fusion_head_bwd")
@@ -310,20 +312,18 @@ class PoolHeadRegionFn(Function):
         h = h.contiguous()
         keep = [_WCACHE.get(hw, cdt), _f32(hb), _f32(ln_w), _f32(ln_b)]
         a = ops.pool_head_args(B, Nt, pool, eps, *keep, drop_mask)
-        need_bwd = bool(grad_enabled) and any(ctx.needs_input_grad)
+        need_bwd = _will_backward(ctx, grad_enabled)
         token, logits, save = ops.pool_head_fwd(a, h, save=need_bwd)
         if need_bwd:
             ctx.args = a
             ctx.keep = (keep, save, h, drop_mask)
             ctx.x_version = h._version
             ctx.params = (ln_w, ln_b, hw, hb)
-        else:
-            ctx.keep = ctx.args = None
         return token, logits
 
     @staticmethod
     def backward(ctx, dtoken, dlogits):
-        _region_state(ctx, "PoolHeadRegionFn", ctx.keep[2] if ctx.keep is not None else None)
+        _region_state(ctx, "PoolHeadRegionFn", 2)
         a = ctx.args
         keep, save, h, drop_mask = ctx.keep
         ln_w, ln_b, hw, hb = ctx.params
@@ -370,8 +370,7 @@ class AggBlockRegionFn(Function):
                 setattr(a.sets[i], f, t.data_ptr())
         save = torch.empty((lib.devias_agg_block_save_bytes(_ct.byref(a)),), dtype=torch.uint8, device=dev)
         a.save = save.data_ptr()
-        ws = ops.workspace(lib.devias_agg_block_workspace_bytes(_ct.byref(a)), dev)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        ops.attach_workspace(a, lib.devias_agg_block_workspace_bytes(_ct.byref(a)), dev)
         slots = torch.empty((B * S, D), dtype=cdt, device=dev)
         attn_ptr = _ct.c_void_p()
         _L.check(lib.devias_agg_block_fwd(_ct.byref(a), x.data_ptr(), slots.data_ptr(), _ct.byref(attn_ptr), ops._stream()), "devias_agg_block_fwd")
@@ -390,7 +389,7 @@ class AggBlockRegionFn(Function):
     def backward(ctx, dslots, dattn):
         B, N, S, depth, tied, heads, dh, eps_enc, eps_agg, cdt = ctx.meta
         lib = _L.load()
-        _region_state(ctx, "AggBlockRegionFn", ctx.keep[2] if ctx.keep is not None else None)
+        _region_state(ctx, "AggBlockRegionFn", 2)
         a = ctx.args
         keep, save, x = ctx.keep
         norm_w, norm_b, latents, last_w, last_b, LP = ctx.params
@@ -408,8 +407,7 @@ class AggBlockRegionFn(Function):
         for i in range(nset):
             for f, ptr in zip(_L.AGG_GRAD_FIELDS, ptrs[6 + nk * i:6 + nk * (i + 1)]):
                 setattr(g.sets[i], f, ptr)
-        ws = ops.workspace(a.ws_bytes, dev)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        ops.attach_workspace(a, a.ws_bytes, dev)
         scr = _scratch(lib.devias_agg_block_scratch_bytes(_ct.byref(a)), dev)
         dslots = dslots.contiguous()
         dattn = dattn.contiguous() if dattn is not None else None

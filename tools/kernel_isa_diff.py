@@ -45,11 +45,14 @@ def compile_unit(job):
 def key_of(mangled):
     """'_ZN12_GLOBAL__N_115gemm256p_kernelILb0ELi8EEEvN2ns1PE' -> 'gemm256p_kernelILb0ELi8EE': the kernel's name and its template arguments as mangled,
     without the enclosing namespaces and the parameter types (which name the namespace of the parameter's type)"""
-    j = 3 if mangled.startswith("_ZN") else 2
+    nested = mangled.startswith("_ZN")
+    j = 3 if nested else 2
     while mangled[j].isdigit():            # the nested name's components, <length><identifier> each: the last one is the kernel
         m = re.match(r"\d+", mangled[j:])
         i = j + m.end()
         name, j = mangled[i:i + int(m.group())], i + int(m.group())
+        if not nested:                     # an unnested name is ONE component: a digit behind it starts the first parameter's type (_Z18reduce_jobs_kernel10ReduceJobs)
+            break
     if mangled[j:j + 1] != "I":
         return name
     depth, k = 0, j
