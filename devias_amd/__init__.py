@@ -4,7 +4,7 @@ Importing the package is cheap and GPU-free; the HIP library is loaded on first 
 error (there is no CPU or eager-PyTorch fallback for the hot path)."""
 __version__ = "0.1.0"
 
-__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma"]
+__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss"]
 
 
 def __getattr__(name):
@@ -14,10 +14,17 @@ def __getattr__(name):
         if name == "create_model":
             from . import modeling_slot_fusion  # noqa: F401  (registers the downstream factories: create_model("slot_fusion_vit_base_patch16_224", ...))
             from . import modeling_finetune  # noqa: F401  (registers the plain video ViT: create_model("vit_base_patch16_224", use_mean_pooling=..., ...))
+            from . import modeling_multi_task  # noqa: F401  (registers the two-token multi-task baseline: create_model("disentangle_vit_base_patch16_224", ...))
         return getattr(modeling_slot, name)
     if name in ("slot_fusion_vit_base_patch16_224", "slot_fusion_vit_small_patch16_224", "slot_fusion_vit_large_patch16_224"):
         from . import modeling_slot_fusion
         return getattr(modeling_slot_fusion, name)
+    if name == "disentangle_vit_base_patch16_224":
+        from . import modeling_multi_task
+        return modeling_multi_task.disentangle_vit_base_patch16_224
+    if name == "MultiTaskTrainLoss":           # the baseline's TrainLoss (its engine: devias_amd.engine_for_multi_task)
+        from .multi_task_loss import TrainLoss
+        return TrainLoss
     if name == "TrainLoss":
         from .train_loss import TrainLoss
         return TrainLoss

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 176               # devias_version() of the library these prototypes describe
+ABI_VERSION = 177              # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -94,6 +94,16 @@ class PoolHeadGrads(Structure):      # devias_pool_head_grads
     _fields_ = [("struct_size", c_int32), ("reserved", c_int32)] + [(n, c_void_p) for n in ("dW", "db", "dln_w", "dln_b")]
 
 
+class TwoTokenHeadArgs(Structure):   # devias_two_token_head_args (ABI 177); struct_size = ctypes.sizeof(TwoTokenHeadArgs)
+    _fields_ = [(n, c_int32) for n in ("struct_size", "B", "Nt", "D", "Ca", "Cs", "dtype", "unified")] + [("eps", c_float), ("reserved", c_int32)] + \
+               [(n, c_void_p) for n in ("Wa", "Ws", "ba", "bs", "ln_w", "ln_b", "mask_a", "mask_s", "ws")] + [("ws_bytes", c_int64)]
+
+
+class TwoTokenHeadGrads(Structure):  # devias_two_token_head_grads
+    _fields_ = [("struct_size", c_int32), ("reserved", c_int32)] + [(n, c_void_p) for n in ("dWa", "dba", "dWs", "dbs", "dln_w", "dln_b")]
+
+
+DISTILL_KL, DISTILL_CE = 0, 1        # DEVIAS_DISTILL_KL / DEVIAS_DISTILL_CE
 POOL_MEAN, POOL_CLS = 0, 1           # DEVIAS_POOL_MEAN / DEVIAS_POOL_CLS
 POOL_HEAD_CHUNK = 64                 # DEVIAS_POOL_HEAD_CHUNK: token rows one workgroup of the region's streaming kernels covers
 AGG_MAX_DEPTH = 16                   # DEVIAS_AGG_MAX_DEPTH
@@ -220,6 +230,14 @@ PROTOTYPES = {
     "devias_pool_head_fwd": (c_int, [POINTER(PoolHeadArgs), _P, _P, _P, _P, _P]),
     "devias_pool_head_bwd": (c_int, [POINTER(PoolHeadArgs), _P, _P, _P, _P, POINTER(PoolHeadGrads), _P]),
     "devias_pool_head_launches": (c_int64, []),
+    "devias_two_token_head_workspace_bytes": (c_int64, [_I, _I, _I, _I, _I, _I, _I]),
+    "devias_two_token_head_save_bytes": (c_int64, [_I, _I, _I]),
+    "devias_two_token_head_fwd": (c_int, [POINTER(TwoTokenHeadArgs), _P, _P, _P, _P, _P, _P, _P]),
+    "devias_two_token_head_bwd": (c_int, [POINTER(TwoTokenHeadArgs), _P, _P, _P, _P, _P, _P, POINTER(TwoTokenHeadGrads), _P]),
+    "devias_two_token_head_launches": (c_int64, []),
+    "devias_distill_workspace_bytes": (c_int64, [_I]),
+    "devias_distill_fwd": (c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "devias_distill_bwd": (c_int, [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "devias_agg_block_save_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_scratch_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_workspace_bytes": (c_int64, [POINTER(AggArgs)]),

@@ -184,6 +184,116 @@ def pool_head_launches() -> int:
     return int(_lib.load().devias_pool_head_launches())
 
 
+def two_token_head_args(B: int, Nt: int, eps: float, Wa: torch.Tensor, ba: torch.Tensor, Ws: Optional[torch.Tensor], bs: Optional[torch.Tensor], ln_w: torch.Tensor,
+                        ln_b: torch.Tensor, mask_a: Optional[torch.Tensor] = None, mask_s: Optional[torch.Tensor] = None) -> "_lib.TwoTokenHeadArgs":
+    """devias_two_token_head_args for head weights Wa [Ca, D], Ws [Cs, D] in the compute dtype and fp32 bias / LayerNorm vectors; Ws = bs = None is the unified head
+    (both tokens through Wa).  The workspace is the stream's.  The caller keeps the tensors alive while the struct is in use (it holds raw pointers)."""
+    lib = _lib.load()
+    unified = Ws is None
+    if unified != (bs is None):
+        raise ValueError("two_token_head: Ws and bs are given together (separate heads) or not at all (unified head)")
+    Ca, D = Wa.shape
+    Cs = Ca if unified else Ws.shape[0]
+    dt = dt_code(Wa.dtype)
+    _chk(Wa, "two_token_head.Wa")
+    if not unified:
+        _chk(Ws, "two_token_head.Ws", Wa.dtype)
+        assert Ws.shape[1] == D
+    for n, t, shape in (("ba", ba, (Ca,)), ("bs", bs, (Cs,)), ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,)), ("mask_a", mask_a, (B, D)), ("mask_s", mask_s, (B, D))):
+        if t is not None:
+            _chk(t, "two_token_head." + n, torch.float32)
+            assert tuple(t.shape) == shape, (n, tuple(t.shape), shape)
+    a = _lib.TwoTokenHeadArgs()
+    a.struct_size = ctypes.sizeof(_lib.TwoTokenHeadArgs)
+    a.B, a.Nt, a.D, a.Ca, a.Cs, a.dtype, a.unified, a.eps = B, Nt, D, Ca, Cs, dt, int(unified), eps
+    a.Wa, a.Ws, a.ba, a.bs, a.ln_w, a.ln_b, a.mask_a, a.mask_s = (_p(t) for t in (Wa, Ws, ba, bs, ln_w, ln_b, mask_a, mask_s))
+    nws = lib.devias_two_token_head_workspace_bytes(B, Nt, D, Ca, Cs, int(unified), dt)
+    if nws <= 0:
+        raise NotImplementedError(f"devias_two_token_head: unsupported dims B={B} Nt={Nt} D={D} Ca={Ca} Cs={Cs} (D in 384 / 768 / 1024, B >= 1, Nt >= 2, Ca, Cs >= 2)")
+    attach_workspace(a, nws, Wa.device)
+    return a
+
+
+def two_token_head_fwd(a: "_lib.TwoTokenHeadArgs", h: torch.Tensor, save: bool = True):
+    """devias_two_token_head_fwd: h [B*Nt, D] -> (token_a [B, D], token_s [B, D], logits_a [B, Ca], logits_s [B, Cs], the save arena as a uint8 tensor or None).
+    Unified head: the two logits are the halves of ONE [2B, Ca] tensor (the library's single GEMM writes it)."""
+    lib = _lib.load()
+    _chk(h, "two_token_head.h")
+    assert tuple(h.shape) == (a.B * a.Nt, a.D) and dt_code(h.dtype) == a.dtype
+    attach_workspace(a, a.ws_bytes, h.device)
+    arena = torch.empty((lib.devias_two_token_head_save_bytes(a.B, a.D, a.dtype),), dtype=torch.uint8, device=h.device) if save else None
+    token_a = torch.empty((a.B, a.D), dtype=h.dtype, device=h.device)
+    token_s = torch.empty((a.B, a.D), dtype=h.dtype, device=h.device)
+    if a.unified:
+        both = torch.empty((2 * a.B, a.Ca), dtype=h.dtype, device=h.device)
+        logits_a, logits_s = both[:a.B], both[a.B:]
+    else:
+        logits_a = torch.empty((a.B, a.Ca), dtype=h.dtype, device=h.device)
+        logits_s = torch.empty((a.B, a.Cs), dtype=h.dtype, device=h.device)
+    _lib.check(lib.devias_two_token_head_fwd(ctypes.byref(a), h.data_ptr(), token_a.data_ptr(), token_s.data_ptr(), logits_a.data_ptr(),
+                                             None if a.unified else logits_s.data_ptr(), _p(arena), _stream()), "devias_two_token_head_fwd")
+    return token_a, token_s, logits_a, logits_s, arena
+
+
+def two_token_head_bwd(a: "_lib.TwoTokenHeadArgs", arena: torch.Tensor, dlogits_a: torch.Tensor, dlogits_s: torch.Tensor, dtoken_a: Optional[torch.Tensor],
+                       dtoken_s: Optional[torch.Tensor], dx: torch.Tensor, grads) -> None:
+    """devias_two_token_head_bwd: writes every row of dx [B*Nt, D] and the fp32 gradients `grads` = (dWa [Ca, D], dba [Ca], dWs [Cs, D], dbs [Cs], dln_w [D], dln_b [D]);
+    unified head: dWs = dbs = None"""
+    lib = _lib.load()
+    _chk(dx, "two_token_head.dx")
+    assert tuple(dx.shape) == (a.B * a.Nt, a.D) and dt_code(dx.dtype) == a.dtype
+    for n, t, shape in (("dlogits_a", dlogits_a, (a.B, a.Ca)), ("dlogits_s", dlogits_s, (a.B, a.Cs)), ("dtoken_a", dtoken_a, (a.B, a.D)), ("dtoken_s", dtoken_s, (a.B, a.D))):
+        if t is not None:
+            _chk(t, "two_token_head." + n, dx.dtype)
+            assert tuple(t.shape) == shape, (n, tuple(t.shape), shape)
+    g = _lib.TwoTokenHeadGrads()
+    g.struct_size = ctypes.sizeof(_lib.TwoTokenHeadGrads)
+    for t, shape in zip(grads, ((a.Ca, a.D), (a.Ca,), (a.Cs, a.D), (a.Cs,), (a.D,), (a.D,))):
+        if t is not None:
+            _chk(t, "two_token_head.grad", torch.float32)
+            assert tuple(t.shape) == shape
+    g.dWa, g.dba, g.dWs, g.dbs, g.dln_w, g.dln_b = [_p(t) for t in grads]
+    attach_workspace(a, a.ws_bytes, dx.device)
+    _lib.check(lib.devias_two_token_head_bwd(ctypes.byref(a), arena.data_ptr(), dlogits_a.data_ptr(), dlogits_s.data_ptr(), _p(dtoken_a), _p(dtoken_s), dx.data_ptr(),
+                                             ctypes.byref(g), _stream()), "devias_two_token_head_bwd")
+
+
+def two_token_head_launches() -> int:
+    """devias_two_token_head_fwd / _bwd calls that launched since the last reset (devias_two_token_head_launches); counters(reset=True) resets it too"""
+    return int(_lib.load().devias_two_token_head_launches())
+
+
+def _chk_distill(who, student, teacher):
+    _chk(student, who + ".student")
+    _chk(teacher, who + ".teacher", torch.float32)
+    if student.dim() != 2 or teacher.dim() != 2 or teacher.shape[0] != student.shape[0] or student.shape[0] == 0 or teacher.shape[1] > student.shape[1]:
+        raise ValueError(f"{who}: student [B, C] and teacher [B, Ct <= C] expected, got {tuple(student.shape)} and {tuple(teacher.shape)}")
+    return student.shape[0], student.shape[1], teacher.shape[1]
+
+
+def distill_fwd(student: torch.Tensor, teacher: torch.Tensor, mode: int, weight: float = 1.0):
+    """devias_distill_fwd: student logits [B, C] (fp32 or bf16) against fp32 teacher logits [B, Ct], left-padded with C - Ct columns of (its global minimum - 1)
+    -> (fp32 loss [1], the device scalar that holds the minimum, or None without a pad)"""
+    B, C, Ct = _chk_distill("distill_fwd", student, teacher)
+    lib = _lib.load()
+    loss = torch.empty((1,), dtype=torch.float32, device=student.device)
+    tmin = torch.empty((1,), dtype=torch.float32, device=student.device) if C > Ct else None
+    ws = workspace(lib.devias_distill_workspace_bytes(B), student.device)
+    _lib.check(lib.devias_distill_fwd(student.data_ptr(), teacher.data_ptr(), B, C, Ct, dt_code(student.dtype), int(mode), float(weight), _p(tmin), loss.data_ptr(),
+                                      ws.data_ptr(), _stream()), "devias_distill_fwd")
+    return loss, tmin
+
+
+def distill_bwd(student: torch.Tensor, teacher: torch.Tensor, tmin: Optional[torch.Tensor], g_loss: torch.Tensor, mode: int, weight: float = 1.0) -> torch.Tensor:
+    """devias_distill_bwd: g_loss is the fp32 DEVICE scalar arriving on the loss, tmin the forward's"""
+    B, C, Ct = _chk_distill("distill_bwd", student, teacher)
+    _chk(g_loss, "distill_bwd.g_loss", torch.float32)
+    dz = torch.empty_like(student)
+    _lib.check(_lib.load().devias_distill_bwd(student.data_ptr(), teacher.data_ptr(), B, C, Ct, dt_code(student.dtype), int(mode), float(weight), _p(tmin),
+                                              g_loss.data_ptr(), dz.data_ptr(), _stream()), "devias_distill_bwd")
+    return dz
+
+
 def auto_split_k(M: int, N: int, K: int, bk: int = 64) -> int:
     """Split the long reduction of a weight-gradient GEMM so that (tiles x splits) is just under ONE full round of the kernel that will run it:
     2 slots per CU for the bf16 256x256 kernel counted in 256x128 halves (512 on MI355X), 3 per CU for the 128x128 kernel (768); the CU count

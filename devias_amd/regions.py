@@ -338,6 +338,56 @@ class PoolHeadRegionFn(Function):
         return (dx, dlw, dlb, dW, db, None, None)
 
 
+class TwoTokenHeadRegionFn(Function):
+    """The two-token multi-task baseline's part after the encoder (model/modeling_multi_task.py:318-334) as one devias_two_token_head_fwd / _bwd call: h [B*Nt, D] ->
+    (token_a [B, D], logits_a [B, Ca], token_s [B, D], logits_s [B, Cs]) from rows 0 and Nt - 1 of each clip.  sw = sb = None is the unified head: both tokens go
+    through (hw, hb) in one GEMM and the two logits are the halves of one [2B, Ca] tensor.  meta = (B, Nt, eps, cdt, grad_enabled): grad_enabled is the caller's
+    torch.is_grad_enabled(), read BEFORE apply (see FusionHeadFn): where it is False, or no input requires a gradient, nothing is saved (save = NULL; same bits).
+    mask_a / mask_s: optional fp32 [B, D] of 0 / (1 / keep), fc_dropout's two draws."""
+
+    @staticmethod
+    def forward(ctx, h, ln_w, ln_b, hw, hb, sw, sb, meta, mask_a=None, mask_s=None):
+        B, Nt, eps, cdt, grad_enabled = meta
+        h = h.contiguous()
+        unified = sw is None
+        keep = [_WCACHE.get(hw, cdt), _f32(hb), None if unified else _WCACHE.get(sw, cdt), None if unified else _f32(sb), _f32(ln_w), _f32(ln_b)]
+        a = ops.two_token_head_args(B, Nt, eps, *keep, mask_a, mask_s)
+        need_bwd = _will_backward(ctx, grad_enabled)
+        token_a, token_s, logits_a, logits_s, save = ops.two_token_head_fwd(a, h, save=need_bwd)
+        if need_bwd:
+            ctx.args = a
+            ctx.keep = (keep, save, h, mask_a, mask_s)
+            ctx.x_version = h._version
+            ctx.params = (ln_w, ln_b, hw, hb, sw, sb)
+        return token_a, logits_a, token_s, logits_s
+
+    @staticmethod
+    def backward(ctx, dtoken_a, dlogits_a, dtoken_s, dlogits_s):
+        _region_state(ctx, "TwoTokenHeadRegionFn", 2)
+        a = ctx.args
+        keep, save, h, mask_a, mask_s = ctx.keep
+        ln_w, ln_b, hw, hb, sw, sb = ctx.params
+        dev = h.device
+
+        def ready(t, shape):          # a contiguous, 16-byte aligned tensor (a GEMM operand); zeros where autograd sent nothing
+            if t is None:
+                return torch.zeros(shape, dtype=h.dtype, device=dev)
+            t = t.contiguous()
+            return t.clone() if t.data_ptr() % 16 else t
+
+        dlogits_a, dlogits_s = ready(dlogits_a, (a.B, a.Ca)), ready(dlogits_s, (a.B, a.Cs))
+        dtoken_a = dtoken_a.contiguous() if dtoken_a is not None else None
+        dtoken_s = dtoken_s.contiguous() if dtoken_s is not None else None
+        live = (hw, hb, sw, sb, ln_w, ln_b)
+        gd = _GradDest([(p, tuple(p.shape)) for p in live if p is not None], dev)
+        it = iter(gd.out)
+        dW, db, dWs, dbs, dlw, dlb = [(next(it) if p is not None else None) for p in live]
+        dx = torch.empty_like(h)
+        ops.two_token_head_bwd(a, save, dlogits_a, dlogits_s, dtoken_a, dtoken_s, dx, (dW, db, dWs, dbs, dlw, dlb))
+        ctx.keep = ctx.args = None
+        return (dx, dlw, dlb, dW, db, dWs, dbs, None, None, None)
+
+
 _AGG_MATS = ("to_q", "to_k", "to_v", "to_out_w", "ff0_w", "ff3_w")                      # -> devias_agg_layer_params.Wq Wk Wv Wo W1 W2
 _AGG_VECS = ("to_out_b", "norm_w", "norm_b", "ctx_w", "ctx_b", "ff0_b", "ff3_b", "ffn_w", "ffn_b")   # -> bo norm_w norm_b ctx_w ctx_b b1 b2 ffn_w ffn_b
 # (devias_agg_layer_grads -- dWq dWk dWv dWo dbo dnorm_w dnorm_b dctx_w dctx_b dW1 db1 dW2 db2 dffn_w dffn_b -- is in _LAYER_KEYS order)

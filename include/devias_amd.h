@@ -55,6 +55,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     174 = devias_adamw_step, devias_adamw_multi, devias_adamw_ema_multi take beta1 / beta2 as double (recompile callers),
                                     175 = devias_fusion_head_* (the slot-fusion classifier's head region), devias_softmax_ce_*, devias_region_counter (additive),
                                     176 = devias_pool_head_* (the plain video ViT's pooled-head region), devias_pool_head_launches (additive),
+                                    177 = devias_two_token_head_* (the multi-task baseline's two-token head region), devias_two_token_head_launches, devias_distill_* (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -770,6 +771,64 @@ int64_t devias_pool_head_save_bytes(int32_t B, int32_t D, int32_t dtype);
 int devias_pool_head_fwd(const devias_pool_head_args* a, const void* h, void* token, void* logits, void* save, void* stream);
 int devias_pool_head_bwd(const devias_pool_head_args* a, const void* save, const void* dlogits, const void* dtoken, void* dx, const devias_pool_head_grads* g, void* stream);
 int64_t devias_pool_head_launches(void);
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 177: the two-token multi-task baseline's part after the encoder (model/modeling_multi_task.py: norm(x)[:, 0] and norm(x)[:, -1], fc_dropout on each token, head /
+ * scene_head), one call per direction.
+ *   h T [B*Nt, D], unpadded (exactly B*Nt rows), T = bf16 or fp32, Nt >= 2
+ *   t_a[b], t_s[b] = rows 0 and Nt-1 of clip b
+ *   y_x[b]     = LN(t_x[b]; ln_w, ln_b, eps), two-pass fp32 statistics (x in {a, s}: the one `norm` serves both rows)
+ *   token_x[b] = T(y_x[b])                                                       T [B, D] each
+ *   a_x[b]     = T(y_x[b] * mask_x[b])  (each mask meets the unrounded y)        T, saved stacked [2B, D]: the B action rows, then the B scene rows
+ *   separate heads (unified = 0): logits_a = T(a_a Wa^T + ba) [B, Ca], logits_s = T(a_s Ws^T + bs) [B, Cs]
+ *   unified head   (unified = 1): Ca == Cs == the head's rows; ONE GEMM over the 2B stacked rows against Wa / ba (read once); logits_a receives T [2B, Ca] -- the action
+ *                                 rows, then the scene rows -- and logits_s, Ws, bs, dWs, dbs are ignored
+ * Backward, from dlogits_a T [B, Ca], dlogits_s T [B, Cs] and the optional dtoken_a, dtoken_s T [B, D]: separate heads give dWx = dlogits_x^T a_x and dbx = column sums
+ * of dlogits_x; the unified head gives ONE pair (dWa, dba) over the 2B stacked rows (the two gradients are stacked in the workspace first), summed in a fixed order.
+ * da = dlogits W stays fp32; g = da * mask + dtoken; dln_w = sum_j g x^, dln_b = sum_j g: per-row partials over the 2B rows summed in index order; the LayerNorm's input
+ * gradient is rounded to T ONCE per row and written to rows 0 and Nt-1 of each clip of dx, zeros to every other row: the call writes all B*Nt rows of dx with 16-byte
+ * stores.  No atomics: results are bitwise equal run to run.
+ * Both structs start with struct_size = sizeof(the struct): a mismatch is DEVIAS_EINVAL, like a null pointer, a bad dtype, Ca != Cs under `unified` or a short workspace --
+ * all before anything is launched.  Supported: D in {384, 768, 1024}, B >= 1, Nt >= 2 (B*Nt < 2^31), Ca, Cs >= 2; anything else is DEVIAS_EUNSUPPORTED (the size queries
+ * then return 0).  devias_two_token_head_launches(): _fwd / _bwd calls that passed validation and launched since the last devias_counters_reset().
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t struct_size;                 /* sizeof(devias_two_token_head_args) */
+    int32_t B, Nt, D, Ca, Cs, dtype, unified;
+    float eps;                           /* the model's norm_layer: 1e-6 */
+    int32_t reserved;
+    const void *Wa, *Ws;                 /* T: head [Ca, D], scene_head [Cs, D] */
+    const float *ba, *bs, *ln_w, *ln_b;  /* head.bias [Ca], scene_head.bias [Cs]; norm weight / bias [D] */
+    const float *mask_a, *mask_s;        /* optional fp32 [B, D] each, 0 or 1/keep: fc_dropout's two independent draws */
+    float* ws; int64_t ws_bytes;         /* devias_two_token_head_workspace_bytes() */
+} devias_two_token_head_args;
+typedef struct {
+    int32_t struct_size;                 /* sizeof(devias_two_token_head_grads) */
+    int32_t reserved;
+    float *dWa, *dba, *dWs, *dbs, *dln_w, *dln_b;      /* fp32, written (not accumulated) */
+} devias_two_token_head_grads;
+int64_t devias_two_token_head_workspace_bytes(int32_t B, int32_t Nt, int32_t D, int32_t Ca, int32_t Cs, int32_t unified, int32_t dtype);
+int64_t devias_two_token_head_save_bytes(int32_t B, int32_t D, int32_t dtype);
+/* save: devias_two_token_head_save_bytes() bytes for the backward, or NULL where nobody will ask for one (x^, rstd and a then live in the workspace; same bits).  Layout
+ * of save, each piece rounded up to 256 bytes: x^ fp32 [2B, D]; rstd fp32 [2B]; a T [2B, D]. */
+int devias_two_token_head_fwd(const devias_two_token_head_args* a, const void* h, void* token_a, void* token_s, void* logits_a, void* logits_s, void* save, void* stream);
+int devias_two_token_head_bwd(const devias_two_token_head_args* a, const void* save, const void* dlogits_a, const void* dlogits_s, const void* dtoken_a, const void* dtoken_s,
+                              void* dx, const devias_two_token_head_grads* g, void* stream);
+int64_t devias_two_token_head_launches(void);
+/* The scene term of the baseline's TrainLoss (run_multi_task_finetuning.py:48-68).  student T [B, C]; teacher fp32 [B, Ct], Ct <= C: the teacher row is read as
+ * C - Ct columns of (min over the WHOLE teacher tensor - 1) followed by its Ct logits (the unified head's left pad, :48-52; never materialised).  The forward finds that
+ * minimum in a launch of its own and leaves it in the device scalar `tmin` (may be NULL when C == Ct); the backward reads it from there.
+ *   DEVIAS_DISTILL_KL: loss = weight / B * sum_b sum_c p_t (log p_t - log p_s)   (kl_div, 'batchmean', log_target; the pad columns carry their softmax mass)
+ *   DEVIAS_DISTILL_CE: loss = 1 / B * sum_b (lse_s - z[b, C - Ct + argmax_c teacher[b, c]]), the FIRST index of the maximum; `weight` is not applied
+ * One workgroup per row, fp32 arithmetic, rows summed in index order; ws: devias_distill_workspace_bytes(B).  Backward, g read from the DEVICE scalar g_loss:
+ * dlogits = g weight / B (p_s - p_t) (KL), g / B (p_s - onehot) (CE), rounded to T once.  B >= 1, 2 <= Ct <= C < 2^24, else DEVIAS_EINVAL before any launch. */
+#define DEVIAS_DISTILL_KL 0
+#define DEVIAS_DISTILL_CE 1
+int64_t devias_distill_workspace_bytes(int32_t B);
+int devias_distill_fwd(const void* student, const float* teacher, int32_t B, int32_t C, int32_t Ct, int32_t dtype, int32_t mode, float weight, float* tmin, float* loss,
+                       float* ws, void* stream);
+int devias_distill_bwd(const void* student, const float* teacher, int32_t B, int32_t C, int32_t Ct, int32_t dtype, int32_t mode, float weight, const float* tmin,
+                       const float* g_loss, void* dlogits, void* stream);
 
 /* Final LayerNorm + AggregationBlock with the folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:105-139;
  * agg_block/attention.py:29-40,66-72,108-141): `depth` layers over `tied ? 1 : depth` weight sets; S <= 4 slots. */
