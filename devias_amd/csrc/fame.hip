@@ -28,7 +28,12 @@ __global__ __launch_bounds__(256) void fame_diff_color_kernel(const float* __res
         float cur[3], d = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            cur[c] = __fadd_rn(__fmul_rn(vb[((int64_t)c * T + t) * HW], stdv[c]), mean[c]);      // x * std + mean, two roundings
+            // x * std + mean in two roundings, as the reference's two tensor operations make them (fame.py:118).  The unit is built with -ffp-contract=fast and this
+            // toolchain's __fmul_rn / __fadd_rn are plain `*` / `+`: written with them the pair came out as ONE v_pk_fma_f32 / v_fmamk_f32 (the ema_lerp note of
+            // elementwise.hip).  The empty asm makes the product a value the combiner cannot look through; it emits no instruction.
+            float xs = vb[((int64_t)c * T + t) * HW] * stdv[c];
+            asm("" : "+v"(xs));
+            cur[c] = xs + mean[c];
             sum[c] += cur[c];
             if (t > 0) d += fabsf(prev[c] - cur[c]);
             prev[c] = cur[c];
@@ -276,6 +281,8 @@ extern "C" int devias_fame_blur(const float* in, float* out, int32_t n_img, int3
 extern "C" int devias_fame_seg_refine(const float* blurred, const int16_t* cmap, int32_t n_img, int32_t imgs_per_clip, int32_t HW, float eps,
                                       float* refine, void* stream) {
     DEVIAS_REQUIRE(blurred && cmap && refine && n_img > 0 && imgs_per_clip > 0 && HW >= 10, "devias_fame_seg_refine: bad args");
+    // the reference writes int(0.5 * H * W) and int(0.1 * H * W) (fame.py:49-50): for these two factors that equals the expression below for
+    // every H, W in 4..512 (tests/test_fame_kernel_ref_cpu.py); for a general beta it does not, so num_fg is the caller's (devias_amd/fame.py)
     const int k_fg = (int)(0.5 * HW), k_bg = (int)(0.1 * HW);
     hipLaunchKernelGGL(fame_seg_refine_kernel, dim3(n_img), dim3(SEL_NT), 0, (hipStream_t)stream, blurred, cmap, imgs_per_clip, HW, k_fg, k_bg, eps, refine);
     DEVIAS_CHECK_LAUNCH("devias_fame_seg_refine");
@@ -294,6 +301,9 @@ extern "C" int devias_fame_binarize_pool(const float* blurred, int32_t n_img, in
 extern "C" int devias_fame_mix(const float* video, const uint8_t* binmask, int32_t mask_stride, const int32_t* src, const int32_t* partner,
                                const int32_t* aug, float* out, int32_t B, int32_t CT, int32_t HW, void* stream) {
     DEVIAS_REQUIRE(video && binmask && src && partner && aug && out && video != out && B > 0 && CT > 0 && HW > 0, "devias_fame_mix: bad args");
+    // HW % 4 == 0 takes the kernel's vector path: float4 loads / stores of every video row and uchar4 loads of every mask row
+    DEVIAS_REQUIRE((HW & 3) || (aligned16(video) && aligned16(out) && ((uintptr_t)binmask & 3) == 0 && (mask_stride & 3) == 0),
+                   "devias_fame_mix: with HW %% 4 == 0, video / out must be 16-byte aligned, binmask 4-byte aligned and mask_stride a multiple of 4");
     int gx = (HW / 4 + 255) / 256; if (gx < 1) gx = 1; if (gx > 64) gx = 64;
     hipLaunchKernelGGL(fame_mix_kernel, dim3(gx, CT, B), dim3(256), 0, (hipStream_t)stream, video, binmask, mask_stride, src, partner, aug, out, CT, HW);
     DEVIAS_CHECK_LAUNCH("devias_fame_mix");

@@ -45,7 +45,7 @@ class FAME(nn.Module):
         _call("devias_fame_blur", diffs.data_ptr(), tmp.data_ptr(), B * S, H, W, self.gauss_size, self.gauss_sigma, st)
         _call("devias_fame_seg_refine", tmp.data_ptr(), cmap.data_ptr(), B * S, S, HW, self.eps, diffs.data_ptr(), st)
         _call("devias_fame_blur", diffs.data_ptr(), tmp.data_ptr(), B * S, H, W, self.gauss_size, self.gauss_sigma, st)
-        num_fg = int(self.beta * HW)
+        num_fg = int(self.beta * H * W)                                # fame.py:80, as written: (beta * H) * W rounds differently from beta * (H * W) at some sizes
         if num_fg <= 0:                                                # torch.topk(k=0): an empty foreground
             binmask = torch.zeros(B * S, H, W, dtype=torch.uint8, device=dev)
             pooled = torch.zeros(B * S, (H // 16) * (W // 16), dtype=torch.float32, device=dev)

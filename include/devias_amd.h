@@ -573,6 +573,8 @@ int devias_ema_multi(const devias_opt_tensor* table, const int32_t* chunk_tensor
  *   devias_fame_binarize_pool  per image: the num_fg largest pixels -> 1 (binmask uint8 [n,H,W], may be NULL), pooled[n, (H/pool)*(W/pool)]
  *                            = pool x pool average of the binary mask (fame.py:78-87, 142-148)
  *   devias_fame_mix          out[j] = aug[j] ? (mask[src[j]] ? video[src[j]] : video[partner[j]]) : video[src[j]]   (fame.py:124-138)
+ *                            mask row of clip c starts at binmask + c * mask_stride.  With HW % 4 == 0 the rows are moved as 16-byte vectors:
+ *                            video / out 16-byte aligned, binmask 4-byte aligned and mask_stride % 4 == 0, or the call is refused
  * Top-k selections take the exact k-th value (radix select on the float bits); equal values are taken in index order.
  * ------------------------------------------------------------------------------------------------- */
 int devias_fame_diff_color(const float* video, int32_t B, int32_t T, int32_t H, int32_t W, float* diffs, int16_t* cmap, void* stream);
