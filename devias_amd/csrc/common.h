@@ -20,8 +20,8 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 int devias_set_error(int code, const char* fmt, ...);
 void devias_count(int id);                                  // launch counters (api.hip): DEVIAS_CNT_* of include/devias_amd.h
 void devias_count_region(int id);                           // the second bank (api.hip): DEVIAS_RCNT_*, calls per fused region / loss entry point
-void devias_pool_head_counter_reset();                      // pool_head.hip: the call counter behind devias_pool_head_launches (both banks are closed); devias_counters_reset calls it
-void devias_two_token_head_counter_reset();                 // two_token_head.hip: the call counter behind devias_two_token_head_launches; devias_counters_reset calls it
+void devias_pool_head_counter_reset();                      // token_head.hip: the call counter behind devias_pool_head_launches (both banks are closed); devias_counters_reset calls it
+void devias_two_token_head_counter_reset();                 // token_head.hip: the call counter behind devias_two_token_head_launches; devias_counters_reset calls it
 extern "C" int32_t devias_policy_gemm_cus(void);             // gemm.hip (the GEMM's host side): CUs the big-tile grids count on (device CUs - option gemm_reserve_cus)
 
 // ---- process-wide options ----------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 // What the chain is bound by: B workgroups (12 in the recipe) on 256 CUs and two dozen dependent launches -- the number of launches and the host that issues them,
 // not bandwidth or arithmetic (a [12, 768] row set is 18 KB).  So the new kernels are one workgroup per row with strided scalar loads (D / 256 <= 4 elements per lane, all in
 // registers, no scratch), every statistic a two-pass fp32 block reduction (row_kernels.h: the block reductions and the row LayerNorm's pieces, shared with loss.hip
-// and pool_head.hip), and the GEMMs / weight gradients / column sums go through the library's small-M launchers as csrc/regions.hip does (region_host.h: those calls,
+// and token_head.hip), and the GEMMs / weight gradients / column sums go through the library's small-M launchers as csrc/regions.hip does (region_host.h: those calls,
 // the arena carver, the entry points' checks and dtype dispatch).  No atomics: the per-clip partial sums of the four LayerNorm parameter pairs are reduced
 // over the clips in index order by one launch (devias_flush_deferred), so results are bitwise equal run to run.
 //

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the fused-region units (regions.hip, fusion_head.hip, pool_head.hip): the entry points' argument checks and dtype dispatch, the arena carver,
+// Host-side helpers shared by the fused-region units (regions.hip, fusion_head.hip, token_head.hip, distill.hip): the entry points' argument checks and dtype dispatch, the arena carver,
 // the Python host's automatic split-K choices restated, and the GEMM / weight-gradient / LayerNorm / column-sum calls a region makes with them.  Every unit that includes
 // this file gets its own copy (anonymous namespace); devias_policy_* (regions.hip) export the policies.  The device side of the head units' row kernels: row_kernels.h.
 #pragma once

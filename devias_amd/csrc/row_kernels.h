@@ -1,4 +1,4 @@
-// Device helpers of the one-workgroup-per-row kernels (loss.hip, fusion_head.hip, pool_head.hip): 256 threads = 4 waves per row, every statistic an fp32 block
+// Device helpers of the one-workgroup-per-row kernels (loss.hip, fusion_head.hip, token_head.hip, distill.hip): 256 threads = 4 waves per row, every statistic an fp32 block
 // reduction (DPP wave reduction of common.h + a 4-wave LDS combine in the fixed order sm[0] + sm[1] + sm[2] + sm[3]: results are bitwise equal run to run).
 // Every unit that includes this file gets its own copy (anonymous namespace).
 #pragma once

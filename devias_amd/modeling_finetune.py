@@ -9,7 +9,7 @@ full-tile GEMM kernels; the attention kernels handle the ragged sequence length 
 unpadded tokens and the pooled-head region without a save arena.
 
 Trainable (`self.training and torch.is_grad_enabled()`): PatchEmbedFn, the cls row prepended in cls-token mode, Block.run per block (the slot model's training
-path, unpadded: B * 1569 rows run the 128 x 128 GEMM kernels) and regions.PoolHeadRegionFn (csrc/pool_head.hip) for everything after the encoder."""
+path, unpadded: B * 1569 rows run the 128 x 128 GEMM kernels) and regions.PoolHeadRegionFn (csrc/token_head.hip) for everything after the encoder."""
 from __future__ import annotations
 
 from functools import partial

@@ -7,7 +7,7 @@ norm(x)[:, 0] and norm(x)[:, -1] before fc_dropout.  With `unified_head` one hea
 
 Trainable (`self.training and torch.is_grad_enabled()`): PatchEmbedFn, the cls row prepended and the scene row appended (each parameter + its position row in
 fp32, then cast, as the plain ViT builds its cls row), Block.run per block on the unpadded [B * (N + 2), D] token matrix and regions.TwoTokenHeadRegionFn
-(csrc/two_token_head.hip) for everything after the encoder.  Otherwise (eval(), or under torch.no_grad()) the same path runs without a graph: the blocks take the
+(csrc/token_head.hip) for everything after the encoder.  Otherwise (eval(), or under torch.no_grad()) the same path runs without a graph: the blocks take the
 forward-only region and the head region saves nothing; at zero drop rates the outputs are bitwise the training forward's."""
 from __future__ import annotations
 

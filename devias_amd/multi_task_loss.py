@@ -1,6 +1,6 @@
 """TrainLoss of the two-token multi-task baseline with the reference's interface (run_multi_task_finetuning.py:31-78): the action term is the given criterion
 (devias_amd.losses.LabelSmoothingCrossEntropy / CrossEntropyLoss, unchanged), the scene term distils the frozen teacher's logits into the scene head through
-devias_distill_fwd / _bwd (csrc/two_token_head.hip).  With the unified head the teacher row is read as num_action_classes columns of (the whole teacher tensor's
+devias_distill_fwd / _bwd (csrc/distill.hip).  With the unified head the teacher row is read as num_action_classes columns of (the whole teacher tensor's
 minimum - 1) followed by its logits (:48-52) -- those pad columns carry softmax mass in the KL, as in the reference -- without the padded tensor ever existing."""
 from __future__ import annotations
 

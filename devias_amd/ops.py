@@ -41,6 +41,14 @@ def _chk(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
     return t
 
 
+def _chk_each(who: str, dtype, *items) -> None:
+    """_chk with `dtype` and the shape of every (name, tensor, shape) whose tensor is not None"""
+    for n, t, shape in items:
+        if t is not None:
+            _chk(t, f"{who}.{n}", dtype)
+            assert tuple(t.shape) == tuple(shape), (n, tuple(t.shape), shape)
+
+
 def workspace(nbytes: int, device) -> torch.Tensor:
     """Grow-only fp32 scratch buffer per (device, stream): kernels of one stream are ordered, so a buffer is never shared by
     two launches in flight (the weight-gradient side stream gets its own)."""
@@ -128,17 +136,11 @@ def pool_head_args(B: int, Nt: int, pool: int, eps: float, W: torch.Tensor, bias
     C, D = W.shape
     dt = dt_code(W.dtype)
     _chk(W, "pool_head.W")
-    for n, t, shape in (("bias", bias, (C,)), ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,))):
-        _chk(t, "pool_head." + n, torch.float32)
-        assert tuple(t.shape) == shape, (n, tuple(t.shape), shape)
+    _chk_each("pool_head", torch.float32, ("bias", bias, (C,)), ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,)), ("drop_mask", drop_mask, (B, D)))
     a = _lib.PoolHeadArgs()
     a.struct_size = ctypes.sizeof(_lib.PoolHeadArgs)
     a.B, a.Nt, a.D, a.C, a.dtype, a.pool, a.eps = B, Nt, D, C, dt, pool, eps
-    a.W, a.bias, a.ln_w, a.ln_b = W.data_ptr(), bias.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr()
-    if drop_mask is not None:
-        _chk(drop_mask, "pool_head.drop_mask", torch.float32)
-        assert tuple(drop_mask.shape) == (B, D)
-        a.drop_mask = drop_mask.data_ptr()
+    a.W, a.bias, a.ln_w, a.ln_b, a.drop_mask = (_p(t) for t in (W, bias, ln_w, ln_b, drop_mask))
     nws = lib.devias_pool_head_workspace_bytes(B, Nt, D, C, dt)
     if nws <= 0:
         raise NotImplementedError(f"devias_pool_head: unsupported dims B={B} Nt={Nt} D={D} C={C} (D in 384 / 768 / 1024, B, Nt >= 1, C >= 2)")
@@ -164,14 +166,10 @@ def pool_head_bwd(a: "_lib.PoolHeadArgs", arena: torch.Tensor, dlogits: torch.Te
     lib = _lib.load()
     _chk(dlogits, "pool_head.dlogits"); _chk(dx, "pool_head.dx")
     assert tuple(dlogits.shape) == (a.B, a.C) and tuple(dx.shape) == (a.B * a.Nt, a.D) and dt_code(dx.dtype) == a.dtype and dlogits.dtype == dx.dtype
-    if dtoken is not None:
-        _chk(dtoken, "pool_head.dtoken", dx.dtype)
-        assert tuple(dtoken.shape) == (a.B, a.D)
+    _chk_each("pool_head", dx.dtype, ("dtoken", dtoken, (a.B, a.D)))
+    _chk_each("pool_head", torch.float32, *zip(("grad",) * 4, grads, ((a.C, a.D), (a.C,), (a.D,), (a.D,))))
     g = _lib.PoolHeadGrads()
     g.struct_size = ctypes.sizeof(_lib.PoolHeadGrads)
-    for t, shape in zip(grads, ((a.C, a.D), (a.C,), (a.D,), (a.D,))):
-        _chk(t, "pool_head.grad", torch.float32)
-        assert tuple(t.shape) == shape
     g.dW, g.db, g.dln_w, g.dln_b = [t.data_ptr() for t in grads]
     attach_workspace(a, a.ws_bytes, dx.device)
     _lib.check(lib.devias_pool_head_bwd(ctypes.byref(a), arena.data_ptr(), dlogits.data_ptr(), _p(dtoken), dx.data_ptr(), ctypes.byref(g), _stream()),
@@ -199,10 +197,8 @@ def two_token_head_args(B: int, Nt: int, eps: float, Wa: torch.Tensor, ba: torch
     if not unified:
         _chk(Ws, "two_token_head.Ws", Wa.dtype)
         assert Ws.shape[1] == D
-    for n, t, shape in (("ba", ba, (Ca,)), ("bs", bs, (Cs,)), ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,)), ("mask_a", mask_a, (B, D)), ("mask_s", mask_s, (B, D))):
-        if t is not None:
-            _chk(t, "two_token_head." + n, torch.float32)
-            assert tuple(t.shape) == shape, (n, tuple(t.shape), shape)
+    _chk_each("two_token_head", torch.float32, ("ba", ba, (Ca,)), ("bs", bs, (Cs,)), ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,)), ("mask_a", mask_a, (B, D)),
+              ("mask_s", mask_s, (B, D)))
     a = _lib.TwoTokenHeadArgs()
     a.struct_size = ctypes.sizeof(_lib.TwoTokenHeadArgs)
     a.B, a.Nt, a.D, a.Ca, a.Cs, a.dtype, a.unified, a.eps = B, Nt, D, Ca, Cs, dt, int(unified), eps
@@ -242,16 +238,11 @@ def two_token_head_bwd(a: "_lib.TwoTokenHeadArgs", arena: torch.Tensor, dlogits_
     lib = _lib.load()
     _chk(dx, "two_token_head.dx")
     assert tuple(dx.shape) == (a.B * a.Nt, a.D) and dt_code(dx.dtype) == a.dtype
-    for n, t, shape in (("dlogits_a", dlogits_a, (a.B, a.Ca)), ("dlogits_s", dlogits_s, (a.B, a.Cs)), ("dtoken_a", dtoken_a, (a.B, a.D)), ("dtoken_s", dtoken_s, (a.B, a.D))):
-        if t is not None:
-            _chk(t, "two_token_head." + n, dx.dtype)
-            assert tuple(t.shape) == shape, (n, tuple(t.shape), shape)
+    _chk_each("two_token_head", dx.dtype, ("dlogits_a", dlogits_a, (a.B, a.Ca)), ("dlogits_s", dlogits_s, (a.B, a.Cs)), ("dtoken_a", dtoken_a, (a.B, a.D)),
+              ("dtoken_s", dtoken_s, (a.B, a.D)))
+    _chk_each("two_token_head", torch.float32, *zip(("grad",) * 6, grads, ((a.Ca, a.D), (a.Ca,), (a.Cs, a.D), (a.Cs,), (a.D,), (a.D,))))
     g = _lib.TwoTokenHeadGrads()
     g.struct_size = ctypes.sizeof(_lib.TwoTokenHeadGrads)
-    for t, shape in zip(grads, ((a.Ca, a.D), (a.Ca,), (a.Cs, a.D), (a.Cs,), (a.D,), (a.D,))):
-        if t is not None:
-            _chk(t, "two_token_head.grad", torch.float32)
-            assert tuple(t.shape) == shape
     g.dWa, g.dba, g.dWs, g.dbs, g.dln_w, g.dln_b = [_p(t) for t in grads]
     attach_workspace(a, a.ws_bytes, dx.device)
     _lib.check(lib.devias_two_token_head_bwd(ctypes.byref(a), arena.data_ptr(), dlogits_a.data_ptr(), dlogits_s.data_ptr(), _p(dtoken_a), _p(dtoken_s), dx.data_ptr(),

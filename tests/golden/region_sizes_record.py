@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Record what every arena / scratch / workspace size query of the fused-region units (csrc/regions.hip, fusion_head.hip, pool_head.hip) returns, as
+"""Record what every arena / scratch / workspace size query of the fused-region units (csrc/regions.hip, fusion_head.hip, token_head.hip) returns, as
 tests/golden/region_sizes.json: the table tests/test_region_sizes_cpu.py holds the library to, exactly.
 
     python tests/golden/region_sizes_record.py [path/to/libdevias_amd.so]          # default: the library of this tree
@@ -38,8 +38,14 @@ def cases():
         for B, Nt, D, C in ((1, 1, 384, 2), (2, 65, 1024, 3), (32, 1568, 768, 400), (2, 65, 512, 3)):                      # (the last: an unsupported D, 0)
             out.append(("devias_pool_head_workspace_bytes", [B, Nt, D, C, dt]))
             out.append(("devias_pool_head_save_bytes", [B, D, dt]))
+        for B, Nt, D, Ca, Cs, uni in ((1, 2, 384, 2, 2, 0), (3, 65, 1024, 101, 365, 0), (3, 65, 1024, 101, 101, 1), (32, 1570, 768, 400, 365, 0), (32, 1570, 768, 765, 765, 1),
+                                      (3, 65, 512, 101, 365, 0)):                                                          # (the last: an unsupported D, 0)
+            out.append(("devias_two_token_head_workspace_bytes", [B, Nt, D, Ca, Cs, uni, dt]))
+            out.append(("devias_two_token_head_save_bytes", [B, D, dt]))
     for B in (1, 12):
         out.append(("devias_softmax_ce_workspace_bytes", [B]))
+    for B in (1, 32):
+        out.append(("devias_distill_workspace_bytes", [B]))
     return out
 
 

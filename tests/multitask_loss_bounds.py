@@ -1,4 +1,4 @@
-"""Per-element error bounds against float64 for the distillation kernels of the multi-task baseline's TrainLoss (devias_distill_fwd / _bwd, csrc/two_token_head.hip).
+"""Per-element error bounds against float64 for the distillation kernels of the multi-task baseline's TrainLoss (devias_distill_fwd / _bwd, csrc/distill.hip).
 
 The sibling of slot_loss_bounds.py's matching-loss part (same rules, same measure: excess(out, ref, bound) = max |out - ref| / bound, a test asserts <= 1).  u = U_FP32,
 u_T the unit of the student logits' dtype.  Inputs are exact: the student logits z [B, C] (on T's grid), the fp32 teacher logits t [B, Ct], pad = C - Ct.  One

@@ -1,5 +1,5 @@
 """Plain-PyTorch restatement of the reference's two-token multi-task baseline (model/modeling_multi_task.py:293-334) on oracle/ref_cpu.py's patch embedding and
-encoder block, of the part after the encoder alone (two_token_head: what csrc/two_token_head.hip fuses; tools/multitask_time.py runs it eagerly on the GPU as the
+encoder block, of the part after the encoder alone (two_token_head: what csrc/token_head.hip fuses; tools/multitask_time.py runs it eagerly on the GPU as the
 ATen yardstick) and of the driver's TrainLoss (run_multi_task_finetuning.py:31-78).  tests/golden/make_multitask_goldens.py checks forward() and train_loss()
 against the real reference while it writes the fixtures; a mismatch aborts.
 

@@ -1,5 +1,5 @@
 """Plain-PyTorch restatement of the reference's plain video ViT (model/modeling_finetune.py:273-325) in both pool modes, on oracle/ref_cpu.py's patch embedding and
-encoder block, and of the part after the encoder alone (pool_head: what csrc/pool_head.hip fuses; tools/plainvit_time.py runs it eagerly on the GPU as the ATen
+encoder block, and of the part after the encoder alone (pool_head: what csrc/token_head.hip fuses; tools/plainvit_time.py runs it eagerly on the GPU as the ATen
 yardstick).  tests/golden/make_plainvit_goldens.py checks forward() against the real reference while it writes the fixtures; a mismatch aborts.
 
 P maps the reference's parameter names to tensors; dtype and device follow the inputs."""

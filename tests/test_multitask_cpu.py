@@ -132,7 +132,7 @@ def test_abi_surface_and_struct_layouts(tmp_path):
     for name in SYMBOLS:
         assert name in declared and name in _lib.PROTOTYPES and hasattr(lib, name), name
     assert lib.devias_version() >= 177 and _lib.ABI_VERSION >= 177
-    assert "two_token_head.hip" in build.SOURCES
+    assert "token_head.hip" in build.SOURCES and "distill.hip" in build.SOURCES
     # a counter of its own: neither bank grew
     assert lib.devias_counter(25) == -1 and lib.devias_region_counter(2) == -1
     consts = {n: int(v) for n, v in re.findall(r"#define DEVIAS_DISTILL_(\w+) (\d+)", hdr)}

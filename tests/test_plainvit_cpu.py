@@ -110,7 +110,7 @@ def test_abi_surface_and_struct_layouts(tmp_path):
     for name in POOL_SYMBOLS:
         assert name in declared and name in _lib.PROTOTYPES and hasattr(lib, name), name
     assert lib.devias_version() >= 176 and _lib.ABI_VERSION >= 176
-    assert "pool_head.hip" in build.SOURCES
+    assert "token_head.hip" in build.SOURCES
     # a counter of its own: neither bank grew
     assert lib.devias_counter(25) == -1 and lib.devias_region_counter(2) == -1 and "pool_head" not in _lib.COUNTERS and "pool_head" not in _lib.REGION_COUNTERS
     consts = {n: int(v) for n, v in re.findall(r"#define DEVIAS_POOL_(\w+) (\d+)", hdr)}

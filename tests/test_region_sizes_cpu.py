@@ -29,11 +29,12 @@ def test_the_table_holds_every_case_of_the_recorder():
     for unit in ("encoder_block", "agg_block"):
         assert {f"devias_{unit}_{q}_bytes" for q in ("save", "scratch", "workspace")} <= fns
     assert {"devias_encoder_block_infer_workspace_bytes", "devias_head_save_bytes", "devias_head_workspace_bytes", "devias_fusion_head_save_bytes",
-            "devias_fusion_head_workspace_bytes", "devias_pool_head_save_bytes", "devias_pool_head_workspace_bytes", "devias_softmax_ce_workspace_bytes"} <= fns
+            "devias_fusion_head_workspace_bytes", "devias_pool_head_save_bytes", "devias_pool_head_workspace_bytes", "devias_softmax_ce_workspace_bytes", "devias_two_token_head_save_bytes",
+            "devias_two_token_head_workspace_bytes", "devias_distill_workspace_bytes"} <= fns
 
 
 def test_an_unsupported_row_dimension_sizes_to_zero():
-    heads = [r for r in TABLE if r["fn"].startswith(("devias_fusion_head_", "devias_pool_head_"))]
+    heads = [r for r in TABLE if r["fn"].startswith(("devias_fusion_head_", "devias_pool_head_", "devias_two_token_head_"))]
     bad = [r for r in heads if 512 in r["args"][:-1]]
     assert {r["fn"] for r in bad} == {r["fn"] for r in heads} and all(r["bytes"] == 0 for r in bad)
     assert all(r["bytes"] > 0 for r in TABLE if r not in bad)

@@ -23,42 +23,14 @@ import sys
 
 import torch
 
+from region_timing import block, kernel_summary as fmt, kernels, med
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 DEV = "cuda"
 ENC = dict(num_classes=400, num_scene_classes=365, all_frames=16, num_latents=2, agg_weights_tie=True, agg_depth=8)
-
-
-def block_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def med(v):
-    return "%.3f ms (min %.3f, max %.3f, n = %d)" % (statistics.median(v), min(v), max(v), len(v))
-
-
-def kernel_trace(fn):
-    """(kernels, sum of their device durations in ms) of one profiled call after warm-up -- copies and memsets left out --, or (None, None) where the profiler gives none"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        ev = [e for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and not str(e.name).lower().startswith(("memcpy", "memset"))]
-        if not ev:
-            return None, None
-        return len(ev), sum(e.time_range.elapsed_us() for e in ev) / 1000.0
-    except Exception as e:          # noqa: BLE001
-        print("profiler unavailable:", e)
-        return None, None
 
 
 def steps(B):
@@ -146,8 +118,8 @@ def main():
         torch.cuda.synchronize()
         s1, s2, d = [], [], []
         for _ in range(a.rounds):
-            s1.append(block_ms(slot_step, a.iters)); d.append(block_ms(fus_step, a.iters))
-            s2.append(block_ms(slot_step, a.iters)); d.append(block_ms(fus_step, a.iters))
+            s1.append(block(slot_step, a.iters)[0]); d.append(block(fus_step, a.iters)[0])
+            s2.append(block(slot_step, a.iters)[0]); d.append(block(fus_step, a.iters)[0])
         spread = abs(statistics.median(s1) - statistics.median(s2))
         slot_ms, down_ms = statistics.median(s1 + s2), statistics.median(d)
         verdict = down_ms <= slot_ms + spread
@@ -170,13 +142,13 @@ def main():
         torch.cuda.synchronize()
         f, e = [], []
         for _ in range(a.rounds):
-            f.append(block_ms(fused, 5 * a.iters)); e.append(block_ms(eager, 5 * a.iters))
-        (nf, tf), (ne, te) = kernel_trace(fused), kernel_trace(eager)
+            f.append(block(fused, 5 * a.iters)[0]); e.append(block(eager, 5 * a.iters)[0])
+        kf, ke = kernels(fused), kernels(eager)
+        tf, te = (sum(t for _, t in k) if k else None for k in (kf, ke))
         faster = statistics.median(f) < statistics.median(e) and (tf is None or te is None or tf < te)
         ok &= faster
-        fmt = lambda n, t: "%d kernels, %.3f ms of kernel time in one profiled call" % (n, t) if n is not None else "kernels: not measured"      # noqa: E731
-        lines += ["(b) head region + cross-entropy, forward + backward: fused      issue time per call %s; %s" % (med(f), fmt(nf, tf)),
-                  "                                                     eager ATen issue time per call %s; %s" % (med(e), fmt(ne, te)),
+        lines += ["(b) head region + cross-entropy, forward + backward: fused      issue time per call %s; %s" % (med(f), fmt(kf)),
+                  "                                                     eager ATen issue time per call %s; %s" % (med(e), fmt(ke)),
                   "    the region is %s (issue time %.2fx%s)" % ("faster" if faster else "NOT FASTER", statistics.median(e) / statistics.median(f),
                                                                   ", kernel time %.2fx" % (te / tf) if tf and te else ""),
                   "(c) peak memory of one step: slot recipe %.1f MiB, downstream %.1f MiB (both models and their inputs resident)" % tuple(peaks)]

@@ -6,7 +6,7 @@
       the HOST time to issue one call (host clock around the loop, before the synchronise), and, from one profiled call, the number of kernels and the SUM of their
       device durations (copies and memsets not counted).  The region must not be slower than the ATen composition in device-event time or in kernel time: the tool
       exits 1 otherwise.  Every other figure is reported, not gated.
-  (b) the bytes per second of the two streaming kernels (pool_partial_kernel reads h once and writes the chunk sums; pool_dx_kernel writes dx once), from their
+  (b) the bytes per second of the two streaming kernels (pool_partial_kernel reads h once and writes the chunk sums; head_dx_kernel writes dx once), from their
       durations in that profiled call and byte counts computed from the shapes, beside the project's LayerNorm forward on the same [B * Nt, D] tensor in this
       process (reads and writes it once: the one-pass stream the other two are judged by).
   (c) forward + backward of the plain ViT (mean pooling, LabelSmoothingCrossEntropy) next to the slot model's (TrainLoss with precomputed teacher logits).
@@ -20,9 +20,10 @@ import argparse
 import os
 import statistics
 import sys
-import time
 
 import torch
+
+from region_timing import block, kernel_summary as fmt, kernels, med
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,39 +31,6 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 DEV = "cuda"
 NT, D, C = 1568, 768, 365
-
-
-def block(fn, iters):
-    """(device-event ms per call, host ms to issue one call)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    t1 = time.perf_counter()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters, (t1 - t0) * 1e3 / iters
-
-
-def med(v):
-    return "%.3f ms (min %.3f, max %.3f, n = %d)" % (statistics.median(v), min(v), max(v), len(v))
-
-
-def kernels(fn):
-    """[(name, device ms)] of one profiled call -- copies and memsets left out --, or None where the profiler gives none"""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        ev = [(str(e.name), e.time_range.elapsed_us() / 1000.0) for e in prof.events()
-              if str(getattr(e, "device_type", "")).endswith("CUDA") and not str(e.name).lower().startswith(("memcpy", "memset"))]
-        return ev or None
-    except Exception as e:          # noqa: BLE001
-        print("profiler unavailable:", e)
-        return None
 
 
 def region_pair(B, dtype=torch.bfloat16):
@@ -150,7 +118,6 @@ def main():
     kf, ke = kernels(fused), kernels(eager)
     fd, ed = statistics.median(v[0] for v in f), statistics.median(v[0] for v in e)
     ok = fd <= ed
-    fmt = lambda k: "%d kernels, %.3f ms of kernel time in one profiled call" % (len(k), sum(t for _, t in k)) if k else "kernels: not measured"      # noqa: E731
     if kf and ke:
         ok &= sum(t for _, t in kf) <= sum(t for _, t in ke)
     lines += ["", "(a) region forward + backward: fused      per call %s; host issue %s; %s" % (med([v[0] for v in f]), med([v[1] for v in f]), fmt(kf)),
@@ -166,7 +133,7 @@ def main():
     kl = kernels(ln)
     es, rows = x.element_size(), B * NT
     chunks = (NT + 63) // 64
-    want = {"pool_partial_kernel": rows * D * es + B * chunks * D * 4, "pool_dx_kernel": rows * D * es + B * D * es}
+    want = {"pool_partial_kernel": rows * D * es + B * chunks * D * 4, "head_dx_kernel": rows * D * es + B * D * es}
     lines += ["", "(b) one-pass streams over the [%d, %d] bf16 tensor (bytes from the shapes over the kernel's duration in one profiled call)" % (rows, D)]
     for name, nbytes in want.items():
         t = [ms for n, ms in (kf or []) if name in n]
