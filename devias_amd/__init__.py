@@ -4,7 +4,7 @@ Importing the package is cheap and GPU-free; the HIP library is loaded on first 
 error (there is no CPU or eager-PyTorch fallback for the hot path)."""
 __version__ = "0.1.0"
 
-__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss"]
+__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss", "Mixup", "SoftTargetCrossEntropy"]
 
 
 def __getattr__(name):
@@ -31,6 +31,12 @@ def __getattr__(name):
     if name == "train_class_batch":
         from .engine_for_slot import train_class_batch
         return train_class_batch
+    if name == "Mixup":                        # mixup / cutmix on the device (the engines' mixup_fn)
+        from .mixup import Mixup
+        return Mixup
+    if name == "SoftTargetCrossEntropy":       # the criterion of a mixed batch
+        from .losses import SoftTargetCrossEntropy
+        return SoftTargetCrossEntropy
     if name == "ModelEma":
         from .ema import ModelEma
         return ModelEma

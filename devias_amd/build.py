@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, "libdevias_amd.so")
 GEMM_SOURCES = ["gemm256.hip", "gemm256p.hip", "gemm128_bf16.hip", "gemm128_f32.hip", "gemm_ss.hip", "gemm256w.hip", "gemm_smallm.hip", "gemm_wgrad_group.hip", "gemm.hip"]
 # the attention: its kernel units (attn_common.h says which kernels share one, and why) + the host side (attention.hip)
 ATTN_SOURCES = ["attn_bwd1w.hip", "attn_mfma16.hip", "attn_fwd.hip", "attn_f32.hip", "attention.hip"]
-SOURCES = GEMM_SOURCES + ATTN_SOURCES + ["slot_attn.hip", "layernorm.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "fusion_head.hip", "token_head.hip", "distill.hip", "probe.hip"]
+SOURCES = GEMM_SOURCES + ATTN_SOURCES + ["slot_attn.hip", "layernorm.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "fusion_head.hip", "token_head.hip", "distill.hip", "mixup.hip", "probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HEADERS = ["common.h", "roctx_shim.h", "region_host.h", "row_kernels.h", "attn_common.h", "attn1w.h", "gemm_common.h", "gemm_tile256.h", "gemm128.h", "gemm256p.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wno-unused-result",
@@ -32,6 +32,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=f
 # and a packed fp32 instruction beside MFMAs costs more issue time than the two it replaces (MI355X_MICROARCH.md, per-instruction constants): forward attention -4 %
 # (profiles/r4_packed_fp32.txt)
 FILE_FLAGS = {src: ["-fno-slp-vectorize"] for src in ATTN_SOURCES}
+# the mix is ATen's mul_ / add_ sequence bit for bit: every product rounded on its own, so no contraction into fused multiply-adds in that unit
+FILE_FLAGS["mixup.hip"] = ["-ffp-contract=off"]
 
 
 def _flags(src: str):

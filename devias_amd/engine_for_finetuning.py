@@ -22,13 +22,15 @@ def train_one_epoch(model, criterion, data_loader: Iterable, optimizer, device, 
                     log_writer=None, start_steps: int = 0, lr_schedule_values=None, wd_schedule_values=None, num_training_steps_per_epoch: Optional[int] = None,
                     update_freq: int = 1, grad_sync=None, check_finite_every: int = 50):
     """engine/engine_for_finetuning.py:24-143 on engine_for_slot._run_steps: one host check of the loss every `check_finite_every` micro-batches instead of
-    `loss.item()` and `torch.cuda.synchronize()` at every step.  `loss_scaler` and `log_writer` are accepted and unused (bf16 / fp32 need no loss scale)."""
-    if mixup_fn is not None:
-        raise NotImplementedError("mixup / cutmix (soft targets) are not part of the downstream recipe: it runs with both at 0")
+    `loss.item()` and `torch.cuda.synchronize()` at every step.  `loss_scaler` and `log_writer` are accepted and unused (bf16 / fp32 need no loss scale).  `mixup_fn`:
+    None or a devias_amd.mixup.Mixup (the batch is mixed in place on the device)."""
+    mixup_fn = _es._device_mixup(mixup_fn)
     model.train(True)
 
     def step(batch):
         samples, targets = (t.to(device, non_blocking=True) for t in batch[:2])
+        if mixup_fn is not None:                                  # (:62-63) after the copy to the device; the criterion is then a SoftTargetCrossEntropy
+            samples, targets = mixup_fn(samples, targets)
         loss, _output = train_class_batch(model, samples, targets, criterion)
         return loss, {}
 

@@ -25,15 +25,16 @@ def train_one_epoch(model, scene_model, criterion, data_loader: Iterable, optimi
                     mixup_fn=None, log_writer=None, start_steps: int = 0, lr_schedule_values=None, wd_schedule_values=None,
                     num_training_steps_per_epoch: Optional[int] = None, update_freq: int = 1, grad_sync=None, check_finite_every: int = 50):
     """engine/engine_for_finetuning_scene.py:24-146 on engine_for_slot._run_steps.  The batch's own targets are ignored (:59-63 overwrite them).  `loss_scaler` and
-    `log_writer` are accepted and unused (bf16 / fp32 need no loss scale)."""
-    if mixup_fn is not None:
-        raise NotImplementedError("mixup / cutmix (soft targets) are not built: the scene recipe's hard pseudo-labels run with both at 0")
+    `log_writer` are accepted and unused (bf16 / fp32 need no loss scale).  `mixup_fn`: None or a devias_amd.mixup.Mixup."""
+    mixup_fn = _es._device_mixup(mixup_fn)
     model.train(True)
     scene_model.eval()
 
     def step(batch):
         samples = batch[0].to(device, non_blocking=True)
         targets = scene_targets(scene_model, samples)
+        if mixup_fn is not None:                                  # (:65-66) AFTER the teacher's argmax on the unmixed clip
+            samples, targets = mixup_fn(samples, targets)
         loss, _output = train_class_batch(model, samples, targets, criterion)
         return loss, {}
 

@@ -27,14 +27,15 @@ def train_one_epoch(model, scene_model, train_criterion, data_loader: Iterable, 
                     num_training_steps_per_epoch: Optional[int] = None, update_freq: int = 1, grad_sync=None, check_finite_every: int = 50):
     """engine/engine_for_multi_task.py:27-149 on engine_for_slot._run_steps: batches are (samples, targets, _, _); one host check of the loss every
     `check_finite_every` micro-batches instead of `loss.item()` and `torch.cuda.synchronize()` at every step.  `loss_scaler` and `log_writer` are accepted and unused
-    (bf16 / fp32 need no loss scale)."""
-    if mixup_fn is not None:
-        raise NotImplementedError("mixup / cutmix (soft targets) are not built: the multi-task recipe's hard action labels run with both at 0")
+    (bf16 / fp32 need no loss scale).  `mixup_fn`: None or a devias_amd.mixup.Mixup."""
+    mixup_fn = _es._device_mixup(mixup_fn)
     model.train(True)
     scene_model.eval()
 
     def step(batch):
         samples, targets = (t.to(device, non_blocking=True) for t in batch[:2])
+        if mixup_fn is not None:                                  # (:64-65) student and teacher both see the mixed clip; TrainLoss is given a SoftTargetCrossEntropy
+            samples, targets = mixup_fn(samples, targets)
         loss, _output, loss_dict = train_class_batch(model, scene_model, samples, targets, train_criterion)
         return loss, loss_dict
 

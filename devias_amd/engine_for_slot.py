@@ -26,6 +26,17 @@ def train_class_batch(model, scene_model, samples, target, train_criterion, fg_m
     return total_loss, output, loss_dict
 
 
+def _device_mixup(mixup_fn):
+    """the `mixup_fn` of the plain, scene and multi-task engines: None, or a devias_amd.mixup.Mixup (batch mixed in place by one kernel launch, dense soft target).  Any
+    other callable -- the reference's host-side Mixup among them -- is refused: its nine tensor passes per batch are not built."""
+    if mixup_fn is None:
+        return None
+    from .mixup import Mixup
+    if not isinstance(mixup_fn, Mixup):
+        raise NotImplementedError(f"mixup_fn must be a devias_amd.mixup.Mixup (mixup / cutmix on the device), got {type(mixup_fn).__name__}: no other mixup callable is built")
+    return mixup_fn
+
+
 def _run_steps(step, data_loader, model, optimizer, max_norm, start_steps, lr_schedule_values, wd_schedule_values, num_training_steps_per_epoch, update_freq, grad_sync, check_finite_every, model_ema=None):
     """The part of train_one_epoch that does not depend on the recipe (shared with engine_for_slot_hvu): LR/WD schedule poke, gradient accumulation over
     `update_freq` micro-batches, optional gradient all-reduce (`grad_sync`, devias_amd.parallel), clip + optimizer step, and one host check of the loss

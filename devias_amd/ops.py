@@ -254,6 +254,60 @@ def two_token_head_launches() -> int:
     return int(_lib.load().devias_two_token_head_launches())
 
 
+def mixup_clips(x: torch.Tensor, table) -> torch.Tensor:
+    """devias_mixup_clips: x [B, ..., H, W] (fp32 or bf16, B even) mixed IN PLACE from `table`, a ctypes array of B _lib.MixupRow (host memory: the rows travel as
+    kernel arguments, nothing is copied to the device ahead of the launch); clip i pairs with clip B-1-i"""
+    _chk(x, "mixup_clips.x")
+    if x.dim() < 3 or x.shape[0] < 2 or x.shape[0] % 2 or x.numel() == 0:
+        raise ValueError(f"mixup_clips: x [B, ..., H, W] with an even B >= 2 expected, got {tuple(x.shape)}")
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    if len(table) != B:
+        raise ValueError(f"mixup_clips: the table has {len(table)} rows for {B} clips")
+    _lib.check(_lib.load().devias_mixup_clips(x.data_ptr(), B, x[0].numel() // (H * W), H, W, dt_code(x.dtype), table, _stream()), "devias_mixup_clips")
+    return x
+
+
+def mixup_target(target: torch.Tensor, num_classes: int, on: float, off: float, w_self, w_other) -> torch.Tensor:
+    """devias_mixup_target: int64 labels [B] -> fp32 [B, C], row b = fl(v(y_b) w_self[b]) + fl(v(y_{B-1-b}) w_other[b]) with v = `on` at the label and `off` elsewhere;
+    w_self / w_other are HOST sequences of B floats.  A label outside [0, C) makes its row and the partner row NaN."""
+    _chk(target, "mixup_target.target", torch.int64)
+    B = target.shape[0] if target.dim() == 1 else 0
+    if B == 0 or len(w_self) != B or len(w_other) != B or int(num_classes) < 2:
+        raise ValueError(f"mixup_target: target [B], B weights each and num_classes >= 2 expected, got {tuple(target.shape)}, {len(w_self)}, {len(w_other)}, {num_classes}")
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=target.device)
+    fa = ctypes.c_float * B
+    _lib.check(_lib.load().devias_mixup_target(target.data_ptr(), B, int(num_classes), float(on), float(off), fa(*w_self), fa(*w_other), out.data_ptr(), _stream()),
+               "devias_mixup_target")
+    return out
+
+
+def _chk_soft_ce(who, logits, target):
+    _chk(logits, who + ".logits")
+    _chk(target, who + ".target", torch.float32)
+    if logits.dim() != 2 or target.shape != logits.shape or logits.shape[0] == 0:
+        raise ValueError(f"{who}: logits [B, C] and a soft target [B, C] expected, got {tuple(logits.shape)} and {tuple(target.shape)}")
+    return logits.shape
+
+
+def soft_ce_fwd(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """devias_soft_ce_fwd: mean_b sum_c -t[b, c] log_softmax(z)[b, c] of logits [B, C] (fp32 or bf16) against fp32 soft targets [B, C] -> fp32 loss [1]"""
+    B, C = _chk_soft_ce("soft_ce_fwd", logits, target)
+    lib = _lib.load()
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    ws = workspace(lib.devias_soft_ce_workspace_bytes(B), logits.device)
+    _lib.check(lib.devias_soft_ce_fwd(logits.data_ptr(), target.data_ptr(), B, C, dt_code(logits.dtype), loss.data_ptr(), ws.data_ptr(), _stream()), "devias_soft_ce_fwd")
+    return loss
+
+
+def soft_ce_bwd(logits: torch.Tensor, target: torch.Tensor, g_loss: torch.Tensor) -> torch.Tensor:
+    """devias_soft_ce_bwd: g_loss is the fp32 DEVICE scalar arriving on the loss"""
+    B, C = _chk_soft_ce("soft_ce_bwd", logits, target)
+    _chk(g_loss, "soft_ce_bwd.g_loss", torch.float32)
+    dz = torch.empty_like(logits)
+    _lib.check(_lib.load().devias_soft_ce_bwd(logits.data_ptr(), target.data_ptr(), B, C, dt_code(logits.dtype), g_loss.data_ptr(), dz.data_ptr(), _stream()), "devias_soft_ce_bwd")
+    return dz
+
+
 def _chk_distill(who, student, teacher):
     _chk(student, who + ".student")
     _chk(teacher, who + ".teacher", torch.float32)

@@ -56,6 +56,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     175 = devias_fusion_head_* (the slot-fusion classifier's head region), devias_softmax_ce_*, devias_region_counter (additive),
                                     176 = devias_pool_head_* (the plain video ViT's pooled-head region), devias_pool_head_launches (additive),
                                     177 = devias_two_token_head_* (the multi-task baseline's two-token head region), devias_two_token_head_launches, devias_distill_* (additive),
+                                    178 = devias_mixup_clips, devias_mixup_target (Mixup / CutMix on the device), devias_soft_ce_* (SoftTargetCrossEntropy) (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -831,6 +832,42 @@ int devias_distill_fwd(const void* student, const float* teacher, int32_t B, int
                        float* ws, void* stream);
 int devias_distill_bwd(const void* student, const float* teacher, int32_t B, int32_t C, int32_t Ct, int32_t dtype, int32_t mode, float weight, const float* tmin,
                        const float* g_loss, void* dlogits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 178: Mixup / CutMix on the device (utils/transform/mixup.py: Mixup) and timm's SoftTargetCrossEntropy.
+ * Every mode of the reference pairs clip i with clip j = B-1-i at the same pixel, and both read the ORIGINAL of the other, so a batch mix is one table of B rows:
+ *   kind NONE: the clip stays; MIXUP: x_i = T(x_i * w_self) + T(x_j * w_other), each product and the sum rounded to T (no fused multiply-add: ATen's
+ *   mul_ / add_ sequence bit for bit); CUTMIX: x_i = x_j inside rows [yl, yh) x columns [xl, xh) of every plane (the box is clamped to the plane first: no table
+ *   value makes an address outside a clip).  'batch' mode repeats one row, 'pair' mode copies row i to row j, 'elem' mode has B independent rows.
+ * devias_mixup_clips: x T [B, P, H, W] (P = channels * frames), mixed IN PLACE: one thread owns a 16-byte piece of BOTH clips of a pair, loads both, stores what changed
+ * (one read and one write of what is touched; a pair of two NONE rows is not launched over; a pair without a MIXUP row is touched only in the rows of its boxes).
+ * 16-byte accesses where x and the clip stride are 16-byte aligned and W >= 16 / sizeof(T); a scalar kernel otherwise.  `table` is HOST memory, read before the call
+ * returns: the rows travel to the device as kernel arguments (up to DEVIAS_MIXUP_PAIRS_PER_LAUNCH active pairs per launch), so there is no host-to-device copy to
+ * wait for or to race with.  B >= 2 and even, P, H, W >= 1, P * H * W < 2^31; kind outside the three values, a NaN weight: DEVIAS_EINVAL before any launch.
+ * devias_mixup_target: out fp32 [B, C], out[b, c] = fl(v(y_b, c) * w_self[b]) + fl(v(y_{B-1-b}, c) * w_other[b]), v = `on` at the label, `off` elsewhere
+ * (mixup_target(): y1 * lam + y2 * (1. - lam)), one launch per DEVIAS_MIXUP_TARGET_ROWS_PER_LAUNCH rows; w_self / w_other are HOST arrays [B], passed as kernel
+ * arguments.  Labels are data: a label outside [0, C) is never an index; its row and the partner row that reads it are NaN.
+ * ------------------------------------------------------------------------------------------------- */
+#define DEVIAS_MIX_NONE 0
+#define DEVIAS_MIX_MIXUP 1
+#define DEVIAS_MIX_CUTMIX 2
+#define DEVIAS_MIXUP_PAIRS_PER_LAUNCH 32
+#define DEVIAS_MIXUP_TARGET_ROWS_PER_LAUNCH 256
+typedef struct {
+    int32_t kind;                        /* DEVIAS_MIX_* */
+    float w_self, w_other;               /* MIXUP: lam and 1 - lam as the host rounded them */
+    int32_t yl, yh, xl, xh;              /* CUTMIX: the box */
+    int32_t reserved;
+} devias_mixup_row;                      /* 32 bytes */
+int devias_mixup_clips(void* x, int32_t B, int32_t P, int32_t H, int32_t W, int32_t dtype, const devias_mixup_row* table, void* stream);
+int devias_mixup_target(const int64_t* target, int32_t B, int32_t C, float on, float off, const float* w_self, const float* w_other, float* out, void* stream);
+/* timm's SoftTargetCrossEntropy: loss = mean_b sum_c -t[b, c] log_softmax(z)[b, c]; logits T [B, C] (fp32 or bf16), soft target fp32 [B, C], loss an fp32 device scalar.
+ * One workgroup per row, fp32 statistics, rows summed in index order (no atomics); sum_c t is NOT assumed to be 1: row = lse * sum_c t - sum_c t z (both relative to the
+ * row maximum).  ws: devias_soft_ce_workspace_bytes(B).  Backward: dlogits = g / B (softmax(z) * sum_c t - t), rounded to T once, g read from the DEVICE scalar g_loss.
+ * B >= 1, C >= 2, else DEVIAS_EINVAL before any launch. */
+int64_t devias_soft_ce_workspace_bytes(int32_t B);
+int devias_soft_ce_fwd(const void* logits, const float* target, int32_t B, int32_t C, int32_t dtype, float* loss, float* ws, void* stream);
+int devias_soft_ce_bwd(const void* logits, const float* target, int32_t B, int32_t C, int32_t dtype, const float* g_loss, void* dlogits, void* stream);
 
 /* Final LayerNorm + AggregationBlock with the folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:105-139;
  * agg_block/attention.py:29-40,66-72,108-141): `depth` layers over `tied ? 1 : depth` weight sets; S <= 4 slots. */
