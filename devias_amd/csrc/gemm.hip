@@ -136,6 +136,13 @@ static int gemm_impl(const devias_gemm_args* a, void* stream) {
     DEVIAS_REQUIRE(a->act >= 0 && a->act <= DEVIAS_ACT_DRELU, "devias_gemm: bad act %d", a->act);
     if (a->act == DEVIAS_ACT_DGELU || a->act == DEVIAS_ACT_DRELU)
         DEVIAS_REQUIRE(a->aux_in, "devias_gemm: act %d needs aux_in", a->act);
+    // leading dimensions: a row stride holds at least the row it strides over (include/devias_amd.h, devias_gemm_args)
+    const int a_row = a->trans_a ? a->M : a->K, b_row = a->trans_b ? a->N : a->K;
+    DEVIAS_REQUIRE(a->lda >= a_row, "devias_gemm: lda %d is smaller than a row of A (%d, trans_a %d)", a->lda, a_row, a->trans_a);
+    DEVIAS_REQUIRE(a->ldb >= b_row, "devias_gemm: ldb %d is smaller than a row of B (%d, trans_b %d)", a->ldb, b_row, a->trans_b);
+    DEVIAS_REQUIRE(a->ldc >= a->N, "devias_gemm: ldc %d is smaller than N %d", a->ldc, a->N);
+    if (a->aux_in || a->aux_out) DEVIAS_REQUIRE(a->ld_aux >= a->N, "devias_gemm: ld_aux %d is smaller than N %d", a->ld_aux, a->N);
+    if (a->res) DEVIAS_REQUIRE(a->ldr >= a->N, "devias_gemm: ldr %d is smaller than N %d", a->ldr, a->N);
     const int* opt = devias_options();
     const int es = a->dtype == DEVIAS_BF16 ? 2 : 4;
     const int ch = 16 / es;

@@ -220,6 +220,13 @@ int devias_device_info(int device, int64_t* out5);
  *   c_f32 = 1 with T = bf16 writes C (and reads it under beta) as fp32: weight-gradient GEMMs.
  *   split_k > 1: partial sums go to `ws` (split_k * M * N floats) and a second kernel reduces them in a fixed order and
  *     applies the same epilogue (used for the long-M weight-gradient reductions and the 64-row slot MLP GEMMs).
+ * Leading dimensions (row strides in elements), checked before anything is launched; a smaller value is DEVIAS_EINVAL with the field named in devias_last_error():
+ *   lda    >= a row of A as stored: K, or M under trans_a
+ *   ldb    >= a row of B as stored: K, or N under trans_b
+ *   ldc    >= N
+ *   ld_aux >= N where aux_in or aux_out is given
+ *   ldr    >= N where res is given
+ *   Larger values, and bases that are not 16-byte aligned, are legal: they select the kernel family ("Embedded operands"), never the result.
  * Naming: SURVEY.md section 8(b) sketched this boundary as devias_gemm_bias_act_{fwd,dgrad,wgrad} and devias_patch_embed_{fwd,wgrad}.  They are ONE entry point here:
  *   devias_gemm_bias_act_fwd   = devias_gemm(trans_a 0, trans_b 0, bias, act, aux_out, res)
  *   devias_gemm_bias_act_dgrad = devias_gemm(trans_a 0, trans_b 1, act DGELU / DRELU + aux_in, colsum = the bias gradient)

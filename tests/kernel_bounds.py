@@ -31,7 +31,7 @@ GEMM (devias_gemm, every layout and kernel form; include/devias_amd.h "epilogue 
              float64 before they are summed.  This second term is not in the issue's statement of the bound and makes it several times looser at
              large K and under dGELU (its polynomial term, 5.5e-4 |A B| per addend, dominates): sums taken after the bf16 store are told apart by the
              plain `colsum` epilogue (no activation, small K), not by the dGELU one -- the GPU tests run both on every kernel that fuses the sums.
-             Where devias_gemm falls back to devias_colsum over the stored C (gemm.hip:331) u_out sum|C| on top.
+             Where devias_gemm falls back to devias_colsum over the stored C (gemm.hip:338) u_out sum|C| on top.
 
 LayerNorm (devias_amd/csrc/layernorm.hip: one wave per row, fp32 statistics, two-pass variance, one rounding of the output)
     forward   mean: (D + 2) u sum|x| / D;   rstd: rstd ((D + 8) u / 2 + 4 u + e_mean^2 / (2 (var + eps)))  (two-pass: first order in e_mean vanishes);

@@ -6,6 +6,7 @@ whose plan is ONE uniform round is bitwise devias_gemm's split-K product (same s
 import pytest
 import torch
 
+import embedded_operands as eo
 import kernel_bounds as kb
 from devias_amd import ops
 
@@ -118,5 +119,67 @@ def test_ineligible_lists_are_refused():
         ops.wgrad_group([ops.wgrad_job(dY[:, :128].contiguous(), X, out[:128])], cus=8)
     with pytest.raises(ValueError):            # M not a multiple of the K-tile
         ops.wgrad_group([ops.wgrad_job(dY[:96], X[:96], out)], cus=8)
+    torch.cuda.synchronize()
+    assert torch.equal(out, c_old)
+
+
+# ---- embedded operands (tests/embedded_operands.py): ldy > Nout, ldx > Kin, NaN between and behind the rows of dY and X, dW and the workspace inside canary bands ----
+def _group_call(jobs, cus, ws_tail=0):
+    """devias_wgrad_group with a workspace of exactly the queried size followed by `ws_tail` canary floats; returns the workspace buffer and its used length"""
+    from devias_amd import _lib
+    lib = _lib.load()
+    arr = (_lib.WgradJob * len(jobs))(*jobs)
+    nbytes = lib.devias_wgrad_group_workspace_bytes(arr, len(jobs), cus)
+    assert nbytes >= 0, lib.devias_last_error()
+    ws = torch.full((nbytes // 4 + ws_tail,), eo.CANARY, device=DEV)
+    _lib.check(lib.devias_wgrad_group(arr, len(jobs), cus, ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "devias_wgrad_group")
+    torch.cuda.synchronize()
+    return ws, nbytes // 4
+
+
+@pytest.mark.parametrize("beta", [0.0, 1.0])
+@pytest.mark.parametrize("cus", [8, 16])
+def test_three_jobs_embedded_operands(cus, beta):
+    """the three jobs of test_three_jobs_one_call at M = 512 (cus 8: a split round; 16: another plan) with dY and X at leading dimensions Nout + 8 (j + 1) and
+    Kin + 8 (j + 2): bitwise the dense call's dW, nothing written outside dW or past the workspace's queried size, inputs untouched"""
+    M = 512
+    data = operands(M)
+    dense = run(ops, M, cus, beta)
+    jobs, bands, inputs = [], [], []
+    for j, (dY, X, c_old, _) in enumerate(data):
+        ybuf, yv = eo.embed(dY, dY.shape[1] + 8 * (j + 1), 64, eo.TAIL_ROWS, eo.NAN)
+        xbuf, xv = eo.embed(X, X.shape[1] + 8 * (j + 2), 64, eo.TAIL_ROWS, eo.NAN)
+        src = c_old if beta != 0.0 else torch.full_like(c_old, eo.NAN)              # beta = 0: a dW the call must not read
+        wbuf, wv = eo.embed(src, c_old.shape[1], 64, eo.TAIL_ROWS, eo.CANARY)
+        jobs.append(eo.wgrad_job_raw(yv, xv, wv, beta))
+        assert (jobs[-1].ldy, jobs[-1].ldx) == (dY.shape[1] + 8 * (j + 1), X.shape[1] + 8 * (j + 2))
+        bands.append((wbuf, wv)); inputs += [(ybuf, ybuf.clone()), (xbuf, xbuf.clone())]
+    ops.counters(reset=True)
+    ws, used = _group_call(jobs, cus, ws_tail=65536)
+    assert ops.counters()["gemm256"] == 3
+    assert bool((ws[used:] == eo.CANARY).all()), "a store past the queried workspace size"
+    for j, ((wbuf, wv), want) in enumerate(zip(bands, dense)):
+        assert eo.same_bits(wv, want), f"job {j}: dW differs from the dense call's"
+        assert eo.intact(wbuf, tuple(wv.shape), wv.shape[1], 64, eo.CANARY), f"job {j}: a store outside dW"
+    for buf, before in inputs:
+        assert eo.same_bits(buf, before)
+
+
+def test_bad_leading_dimensions_are_refused():
+    """ldy % 8 != 0, ldy < Nout, ldx < Kin: DEVIAS_EINVAL from the size query and from the call, no counter moved, dW untouched"""
+    from devias_amd import _lib
+    lib = _lib.load()
+    dY, X, c_old, _ = operands(512)[0]
+    out = c_old.clone()
+    ws = torch.empty(1 << 20, device=DEV)
+    for field, value in (("ldy", dY.shape[1] + 4), ("ldy", dY.shape[1] - 8), ("ldx", X.shape[1] - 8)):
+        job = eo.wgrad_job_raw(dY, X, out)
+        setattr(job, field, value)
+        arr = (_lib.WgradJob * 1)(job)
+        before = ops.counters()
+        assert lib.devias_wgrad_group_workspace_bytes(arr, 1, 8) == -1
+        assert lib.devias_wgrad_group(arr, 1, 8, ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream().cuda_stream) == -1        # DEVIAS_EINVAL
+        assert f"{field}={value}" in lib.devias_last_error().decode()
+        assert ops.counters() == before
     torch.cuda.synchronize()
     assert torch.equal(out, c_old)
