@@ -245,7 +245,7 @@ def _weight_sets(layer_params, nset: int):
 # ---- folded aggregation block -------------------------------------------------------------------------------------------------------------
 # sim = scale (Wk_h^T q) . c_j and o = Wv_h sum_j Abar c_j: the to_k / to_v projections move to the slot side (composite D x D weights per head,
 # built once per forward), the per-layer stream is the context c [M, D] instead of K|V [M, 2*h*512], and the K|V GEMM + its dgrad + wgrad vanish
-# (csrc/slot_attn.hip "folded form").  Same parameters, same outputs, same gradients; summation order differs (fp32 round-off).
+# (csrc/slot_valu.hip "folded form", csrc/slot_mfma.hip).  Same parameters, same outputs, same gradients; summation order differs (fp32 round-off).
 def _composites(P, heads, dh, D, cdt):
     """Wqk [h*D, D] (Wqk_h = Wk_h^T Wq_h) and Wov [D, h*D] (Wov_h = Wo_h Wv_h) in the compute dtype, + the operands for their backward"""
     Wq, Wk, Wv, Wo = (_WCACHE.get(P[k], cdt) for k in ("to_q", "to_k", "to_v", "to_out_w"))

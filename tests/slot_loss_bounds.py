@@ -2,28 +2,28 @@
 
 The sibling of kernel_bounds.py (same rules, same measure: excess(out, ref, bound) = max |out - ref| / bound, a test asserts <= 1): a plain helper module, no
 fixtures, no plugin; torch arithmetic on whatever device the arguments live on (the loss reference is the project's CPU oracle and runs on the CPU).  Kernel
-sources are cited by file name: slot_attn.hip and loss.hip live in devias_amd/csrc/.
+sources are cited by file name: slot_unfolded.hip, slot_valu.hip, slot_mfma.hip (below unfolded:, valu:, mfma:) and loss.hip live in devias_amd/csrc/.
 
-Slot attention forward (slot_attn.hip; three kernel families: unfolded slot_fwd_kernel :43, folded VALU slotf_fwd_kernel :380, folded matrix-core slotm_kernel :649)
-    inputs are exact in both dtypes; scores, the slot softmax and all sums are fp32 in every kernel (:82-98, :412-428, :718-759)
+Slot attention forward (three kernel families, one unit each: unfolded slot_fwd_kernel unfolded:38, folded VALU slotf_fwd_kernel valu:56, folded matrix-core slotm_kernel mfma:44)
+    inputs are exact in both dtypes; scores, the slot softmax and all sums are fp32 in every kernel (unfolded:77-93, valu:88-104, mfma:113-154)
     sim   = scale q.k                        e_sim = (Dk + 8) u_fp32 T_ij,  T_ij = scale sum_d |q_id||k_jd|   (Dk = 512 unfolded, D folded)
     A     = softmax over the SLOT axis       e_A   = a_i (e_sim_ij + sum_i' a_i' e_sim_i'j + (8 + max_i' sim_i'j - sim_ij) u_fp32)   (expf of a rounded difference, divide)
-    rsum  = sum_j A + 1e-7                   e_r   = (N + 8) u_fp32 sum_j a + sum_j e_A + 2 u_fp32 rsum   (:135, :480: the addition of 1e-7 and the constant's own rounding)
-    o / z = sum_j (A / rsum) v_j             u_out |o| + (N + 8) u_fp32 sum_j abar |v_j| + sum_j e_abar |v_j|,  e_abar = (e_A + abar e_r) / rsum     (:140, :484: one rounding)
-    slotm_kernel additionally                u_bf16 sum_j abar_ij |c_j|: A is packed to bf16 for the Z product (:779) while rsum sums the fp32 A (:759) -- no cancellation
-Slot attention backward (on the SAVED attn, rsum and the stored o / z the kernel is given; slot_bwd_kernel :148, slotf_bwd_kernel :490, slotm_kernel<BWD>)
-    delta_i = dO_i . o_i                     (Dv + 8) u_fp32 sum_d |dO o|                                   (:166-169, :506-509, :680-689)
-    dA    = (dAbar - delta) rinv + dA_ext    rinv ((Dv + 8) u_fp32 (|dO|.|v_j| + sum|dO o|) + 4 u_fp32 (|dAbar| + |delta|)) + 2 u_fp32 |dA_ext|   (:200, :535, :761)
-    ds    = a (dA - sum_i a dA)              a (e_dA + sum_i a e_dA + (S + 2) u_fp32 sum_i a |dA| + 3 u_fp32 (|dA| + sum_i a |dA|)); fp32, stored unrounded (:208, :543, :772)
-    dq    = scale sum_j ds k_j               u_out |dq| + scale sum_j e_ds |k_j| + (N + 8) u_fp32 scale sum_j |ds||k_j|     (one rounding: :242, :576)
-    slotm_kernel additionally                u_bf16 scale sum_j |ds_ij||c_j|: scale dS is packed to bf16 for the dQ' product (:777-779)
+    rsum  = sum_j A + 1e-7                   e_r   = (N + 8) u_fp32 sum_j a + sum_j e_A + 2 u_fp32 rsum   (unfolded:130, valu:156: the addition of 1e-7 and the constant's own rounding)
+    o / z = sum_j (A / rsum) v_j             u_out |o| + (N + 8) u_fp32 sum_j abar |v_j| + sum_j e_abar |v_j|,  e_abar = (e_A + abar e_r) / rsum     (unfolded:135, valu:160: one rounding)
+    slotm_kernel additionally                u_bf16 sum_j abar_ij |c_j|: A is packed to bf16 for the Z product (mfma:174) while rsum sums the fp32 A (mfma:154) -- no cancellation
+Slot attention backward (on the SAVED attn, rsum and the stored o / z the kernel is given; slot_bwd_kernel unfolded:141, slotf_bwd_kernel valu:166, slotm_kernel<BWD>)
+    delta_i = dO_i . o_i                     (Dv + 8) u_fp32 sum_d |dO o|                                   (unfolded:159-162, valu:182-185, mfma:75-84)
+    dA    = (dAbar - delta) rinv + dA_ext    rinv ((Dv + 8) u_fp32 (|dO|.|v_j| + sum|dO o|) + 4 u_fp32 (|dAbar| + |delta|)) + 2 u_fp32 |dA_ext|   (unfolded:193, valu:211, mfma:156)
+    ds    = a (dA - sum_i a dA)              a (e_dA + sum_i a e_dA + (S + 2) u_fp32 sum_i a |dA| + 3 u_fp32 (|dA| + sum_i a |dA|)); fp32, stored unrounded (unfolded:201, valu:219, mfma:167)
+    dq    = scale sum_j ds k_j               u_out |dq| + scale sum_j e_ds |k_j| + (N + 8) u_fp32 scale sum_j |ds||k_j|     (one rounding: unfolded:235, valu:252)
+    slotm_kernel additionally                u_bf16 scale sum_j |ds_ij||c_j|: scale dS is packed to bf16 for the dQ' product (mfma:172-174)
     All sums of ABSOLUTE terms: a result that cancels (dAbar against delta, dA against its slot mean) is held to the size of what was subtracted.
 Deferred gradients (factor 1, rigorous)
-    devias_slot_attn_kv_grad (:253)          u_out |r| + (L S + 8) u_fp32 sum |coef||vec|, and in bf16 ONE MORE u_out |running value| per completed group of 16
-                                             (layer, slot) pairs: the kernel stores dk / dv (:320-321) and re-loads them (:302) between groups.  Named here, not
+    devias_slot_attn_kv_grad (unfolded:244)          u_out |r| + (L S + 8) u_fp32 sum |coef||vec|, and in bf16 ONE MORE u_out |running value| per completed group of 16
+                                             (layer, slot) pairs: the kernel stores dk / dv (unfolded:311-312) and re-loads them (unfolded:293) between groups.  Named here, not
                                              removed: keeping the running sums in registers needs every pair's q / dO in LDS at once (128 KB at L S = 32), and an
                                              fp32 side buffer costs a second [B N, 2 h 512] stream; both cost more than the rounding is worth.
-    slotf_context_grad (ops.py)              devias_slotf_pack rounds A / rsum and scale ds to the operand dtype (:597, :599): (u_dt + 3 u_fp32) sum |coef||vec|; the
+    slotf_context_grad (ops.py)              devias_slotf_pack rounds A / rsum and scale ds to the operand dtype (valu:273, valu:275): (u_dt + 3 u_fp32) sum |coef||vec|; the
                                              batched GEMM carries kernel_bounds' GEMM bound with K = 2 L h S: u_out |dc| + (K + 8) u_fp32 sum |coef||vec|
 Matching loss (loss.hip; one workgroup per sample, fp32 statistics, block sums of 256 threads: a sum over n addends carries (n / 256 + 12) u_fp32)
     lse   = mx + logf(sum expf(z - mx))      e_lse = u_fp32 (sum_c p_c (|z_c - mx| + 3) + C / 256 + 12 + 2 |lse| + 2 |mx|)          (row_stats :48-55)
@@ -65,7 +65,7 @@ SLACK_SLOT_BWD = 2 * 0.8468    # the emulation needs 0.84674
 SLACK_LOSS = 2 * 0.995         # the emulation needs 0.994 (a bf16 store of dZ / d_slots)
 EPS_RSUM = 1e-7
 SLOT_SCALE = 512 ** -0.5
-KVG_PAIRS = 16                  # slot_attn.hip:251
+KVG_PAIRS = 16                  # slot_unfolded.hip:242
 MATCH_MARGIN = 0.05
 SLOT_GENERATORS = ("diffuse", "peaked", "offset", "starved")
 
@@ -249,7 +249,7 @@ def slot_bwd_ref(src, attn, rsum, o, d_o, dA_ext, B, S, N, h, scale, dtype, fold
 
 
 def _pairs(t, L, B, S, h):
-    """[L, B S, h D] -> float64 [B, h, L S, D], pair p = l S + i (the kernel's order, slot_attn.hip:272)"""
+    """[L, B S, h D] -> float64 [B, h, L S, D], pair p = l S + i (the kernel's order, slot_unfolded.hip:263)"""
     return t.double().reshape(L, B, S, h, -1).permute(1, 3, 0, 2, 4).reshape(B, h, L * S, -1)
 
 
@@ -268,7 +268,7 @@ def slot_kv_grad_ref(q_stack, do_stack, ds_stack, attn_stack, rsum_stack, L, B, 
         ref = coef.transpose(-1, -2) @ vec
         bound = uo * ref.abs() + (P + 8) * u * (coef.abs().transpose(-1, -2) @ vec.abs())
         if dtype == torch.bfloat16 and inter_group:
-            for p1 in range(KVG_PAIRS, P, KVG_PAIRS):              # the value stored after each completed group but the last (slot_attn.hip:302, 320)
+            for p1 in range(KVG_PAIRS, P, KVG_PAIRS):              # the value stored after each completed group but the last (slot_unfolded.hip:293, 311)
                 bound = bound + uo * (coef[:, :, :p1].transpose(-1, -2) @ vec[:, :, :p1]).abs()
         parts.append((ref, bound))
     pack = lambda i: torch.stack([parts[0][i], parts[1][i]], dim=2).permute(0, 3, 2, 1, 4).reshape(B * N, -1)  # noqa: E731  [B, h, 2, N, dh] -> [B N, 2 h dh]

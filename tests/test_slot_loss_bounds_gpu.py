@@ -103,7 +103,7 @@ def test_slotf_valu(dtype, S, h, D):
 @pytest.mark.parametrize("S", [2, 3, 4, 5, 8])
 @pytest.mark.parametrize("dtype", [F32, BF])
 def test_slot_unfolded(dtype, S, h):
-    """S covers the three register forms (MAXS 2, 4, 8: slot_attn.hip:826-828).  N: a ragged chunk, exactly one 64-token chunk, one token into the second, two into the third"""
+    """S covers the three register forms (MAXS 2, 4, 8: slot_unfolded.hip:318-319).  N: a ragged chunk, exactly one 64-token chunk, one token into the second, two into the third"""
     slot_sweep("slot", False, dtype, 2, S, h, 512, (7, 64, 65, 130))
 
 
