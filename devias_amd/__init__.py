@@ -4,7 +4,7 @@ Importing the package is cheap and GPU-free; the HIP library is loaded on first 
 error (there is no CPU or eager-PyTorch fallback for the hot path)."""
 __version__ = "0.1.0"
 
-__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss", "Mixup", "SoftTargetCrossEntropy"]
+__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss", "Mixup", "SoftTargetCrossEntropy", "ClipIngest", "IngestLoader"]
 
 
 def __getattr__(name):
@@ -37,6 +37,9 @@ def __getattr__(name):
     if name == "SoftTargetCrossEntropy":       # the criterion of a mixed batch
         from .losses import SoftTargetCrossEntropy
         return SoftTargetCrossEntropy
+    if name in ("ClipIngest", "IngestLoader"):  # uint8 frames to the normalised, cropped, resized clip on the device; the loader wrapper that feeds the engines
+        from . import ingest
+        return getattr(ingest, name)
     if name == "ModelEma":
         from .ema import ModelEma
         return ModelEma

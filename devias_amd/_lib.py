@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 178              # devias_version() of the library these prototypes describe
+ABI_VERSION = 179              # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -107,9 +107,15 @@ class MixupRow(Structure):          # devias_mixup_row (ABI 178): 32 bytes
     _fields_ = [("kind", c_int32), ("w_self", c_float), ("w_other", c_float)] + [(n, c_int32) for n in ("yl", "yh", "xl", "xh", "reserved")]
 
 
+class IngestRow(Structure):         # devias_ingest_row (ABI 179): 40 bytes
+    _fields_ = [("offset", c_int64)] + [(n, c_int32) for n in ("H0", "W0", "i", "j", "h", "w", "flip", "reserved")]
+
+
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2     # DEVIAS_MIX_*
 MIXUP_PAIRS_PER_LAUNCH = 32          # DEVIAS_MIXUP_PAIRS_PER_LAUNCH
 MIXUP_TARGET_ROWS_PER_LAUNCH = 256   # DEVIAS_MIXUP_TARGET_ROWS_PER_LAUNCH
+INGEST_ROWS_PER_LAUNCH = 32          # DEVIAS_INGEST_ROWS_PER_LAUNCH
+INGEST_MAX_SIDE = 16384              # DEVIAS_INGEST_MAX_SIDE
 DISTILL_KL, DISTILL_CE = 0, 1        # DEVIAS_DISTILL_KL / DEVIAS_DISTILL_CE
 POOL_MEAN, POOL_CLS = 0, 1           # DEVIAS_POOL_MEAN / DEVIAS_POOL_CLS
 POOL_HEAD_CHUNK = 64                 # DEVIAS_POOL_HEAD_CHUNK: token rows one workgroup of the region's streaming kernels covers
@@ -250,6 +256,7 @@ PROTOTYPES = {
     "devias_soft_ce_workspace_bytes": (c_int64, [_I]),
     "devias_soft_ce_fwd": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "devias_soft_ce_bwd": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "devias_clip_ingest": (c_int, [_P, _L, _P, POINTER(IngestRow), _I, _I, _I, _I, _I, _P, _P]),
     "devias_agg_block_save_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_scratch_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_workspace_bytes": (c_int64, [POINTER(AggArgs)]),

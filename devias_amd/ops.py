@@ -281,6 +281,19 @@ def mixup_target(target: torch.Tensor, num_classes: int, on: float, off: float, 
     return out
 
 
+def clip_ingest(src: torch.Tensor, table: torch.Tensor, rows, T: int, out: torch.Tensor) -> torch.Tensor:
+    """devias_clip_ingest: src a flat uint8 device buffer, table the fp32 [3, 256] device tap table, rows a ctypes array of B _lib.IngestRow (host memory: the rows
+    travel as kernel arguments), out [B, 3, T, S_h, S_w] fp32 or bf16 (any base alignment: a view into a larger allocation is served by the scalar kernel)"""
+    _chk(src, "clip_ingest.src", torch.uint8)
+    _chk(table, "clip_ingest.table", torch.float32)
+    _chk(out, "clip_ingest.out")
+    if src.dim() != 1 or table.numel() != 768 or out.dim() != 5 or out.shape[0] != len(rows) or out.shape[1] != 3 or out.shape[2] != int(T):
+        raise ValueError(f"clip_ingest: a flat src, a 768-entry table and out [B={len(rows)}, 3, T={T}, S_h, S_w] expected, got {tuple(src.shape)}, {tuple(table.shape)}, {tuple(out.shape)}")
+    _lib.check(_lib.load().devias_clip_ingest(src.data_ptr(), src.numel(), table.data_ptr(), rows, out.shape[0], int(T), out.shape[3], out.shape[4], dt_code(out.dtype),
+                                              out.data_ptr(), _stream()), "devias_clip_ingest")
+    return out
+
+
 def _chk_soft_ce(who, logits, target):
     _chk(logits, who + ".logits")
     _chk(target, who + ".target", torch.float32)

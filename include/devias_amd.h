@@ -57,6 +57,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     176 = devias_pool_head_* (the plain video ViT's pooled-head region), devias_pool_head_launches (additive),
                                     177 = devias_two_token_head_* (the multi-task baseline's two-token head region), devias_two_token_head_launches, devias_distill_* (additive),
                                     178 = devias_mixup_clips, devias_mixup_target (Mixup / CutMix on the device), devias_soft_ce_* (SoftTargetCrossEntropy) (additive),
+                                    179 = devias_clip_ingest (clip ingest on the device: uint8 frames to normalised, cropped, resized, flipped clips) (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -875,6 +876,36 @@ int devias_mixup_target(const int64_t* target, int32_t B, int32_t C, float on, f
 int64_t devias_soft_ce_workspace_bytes(int32_t B);
 int devias_soft_ce_fwd(const void* logits, const float* target, int32_t B, int32_t C, int32_t dtype, float* loss, float* ws, void* stream);
 int devias_soft_ce_bwd(const void* logits, const float* target, int32_t B, int32_t C, int32_t dtype, const float* g_loss, void* dlogits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 179: clip ingest on the device -- what the reference's workers do between RandAugment and the collate (dataset/kinetics.py:257-284: ToTensor, tensor_normalize,
+ * video_transforms.random_resized_crop, horizontal_flip) and between the short-side Resize and the collate of validation / test (CenterCrop or the view's window,
+ * ClipToTensor, Normalize).
+ * devias_clip_ingest: src one flat uint8 DEVICE buffer of src_bytes bytes; clip b's frames [T, H0, W0, 3] (the decoder's THWC layout) start rows[b].offset bytes in, and
+ * clips of one batch may differ in H0 and W0.  out T [B, 3, T, S_h, S_w] (fp32 or bf16), out[b, c, t, y, x] = the bilinear resize (half-pixel rule, align_corners=False) of
+ * the box rows [i, i+h) x columns [j, j+w) of channel c of frame t to S_h x S_w, read at column S_w-1-x where flip is set (the flip acts after the resize).
+ *   taps     table[c * 256 + u] (fp32 [3, 256] DEVICE memory, built once by the caller as fl(fl(fl(u / 255) - mean_c) / std_c)): no arithmetic on a pixel but the lookup
+ *   coords   output index d of n_out over a run of n_in: src = max((d + 0.5) n_in / n_out - 0.5, 0) from integers: ((2d + 1) n_in - n_out) / (2 n_out) gives the first
+ *            tap i0 as quotient and lambda as remainder / (2 n_out), rounded once; i1 = min(i0 + 1, n_in - 1)
+ *   value    fl(fl(wy0 fl(fl(wx0 a) + fl(wx1 b))) + fl(wy1 fl(fl(wx0 c) + fl(wx1 d)))), w1 = lambda, w0 = fl(1 - lambda); bf16 output rounds that once more.
+ *            A box with h = S_h and w = S_w has every lambda 0: the output is the table's taps bit for bit.
+ * One thread owns a run of output columns of one (clip, frame, row) for all three channels and stores each plane with a 16-byte store where out is 16-byte aligned and
+ * S_w is a multiple of 16 / sizeof(T); a scalar kernel serves everything else.  `rows` is HOST memory, read before the call returns: the rows travel as kernel arguments,
+ * DEVIAS_INGEST_ROWS_PER_LAUNCH clips per launch, so there is no table copy to wait for and no host synchronisation.
+ * Checked before any launch (DEVIAS_EINVAL): null pointers; B, T, S_h, S_w < 1 or a side above DEVIAS_INGEST_MAX_SIDE; T S_h S_w >= 2^31; an unknown out_dtype; a box
+ * that is empty or leaves its frame; flip outside {0, 1}; a clip whose offset + T H0 W0 3 exceeds src_bytes.  No row makes an address outside [src, src + src_bytes).
+ * ------------------------------------------------------------------------------------------------- */
+#define DEVIAS_INGEST_ROWS_PER_LAUNCH 32
+#define DEVIAS_INGEST_MAX_SIDE 16384
+typedef struct {
+    int64_t offset;                      /* byte offset of the clip's [T, H0, W0, 3] frames in src */
+    int32_t H0, W0;                      /* the frames' size */
+    int32_t i, j, h, w;                  /* the box: rows [i, i+h), columns [j, j+w) */
+    int32_t flip;                        /* 1: the output columns are reversed */
+    int32_t reserved;
+} devias_ingest_row;                     /* 40 bytes */
+int devias_clip_ingest(const void* src, int64_t src_bytes, const float* table, const devias_ingest_row* rows, int32_t B, int32_t T, int32_t S_h, int32_t S_w,
+                       int32_t out_dtype, void* out, void* stream);
 
 /* Final LayerNorm + AggregationBlock with the folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:105-139;
  * agg_block/attention.py:29-40,66-72,108-141): `depth` layers over `tied ? 1 : depth` weight sets; S <= 4 slots. */
