@@ -4,7 +4,7 @@ Importing the package is cheap and GPU-free; the HIP library is loaded on first 
 error (there is no CPU or eager-PyTorch fallback for the hot path)."""
 __version__ = "0.1.0"
 
-__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss", "Mixup", "SoftTargetCrossEntropy", "ClipIngest", "IngestLoader"]
+__all__ = ["create_model", "VisionTransformer", "TrainLoss", "train_class_batch", "ModelEma", "disentangle_vit_base_patch16_224", "MultiTaskTrainLoss", "Mixup", "SoftTargetCrossEntropy", "ClipIngest", "IngestLoader", "RandAugment"]
 
 
 def __getattr__(name):
@@ -40,6 +40,9 @@ def __getattr__(name):
     if name in ("ClipIngest", "IngestLoader"):  # uint8 frames to the normalised, cropped, resized clip on the device; the loader wrapper that feeds the engines
         from . import ingest
         return getattr(ingest, name)
+    if name == "RandAugment":                   # the recipe's RandAugment on the staged uint8 frames, before the ingest
+        from .randaug import RandAugment
+        return RandAugment
     if name == "ModelEma":
         from .ema import ModelEma
         return ModelEma

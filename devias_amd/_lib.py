@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("DEVIAS_LIB_PATH") or os.path.join(_HERE, "libdevias_a
 
 F32, BF16 = 0, 1
 ATTN_Q_PRESCALED = 1                # DEVIAS_ATTN_Q_PRESCALED (devias_mhsa_*_flags)
-ABI_VERSION = 179              # devias_version() of the library these prototypes describe
+ABI_VERSION = 180              # devias_version() of the library these prototypes describe
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SIGMOID, ACT_DGELU, ACT_DRELU = 0, 1, 2, 3, 4, 5
 
 
@@ -111,11 +111,17 @@ class IngestRow(Structure):         # devias_ingest_row (ABI 179): 40 bytes
     _fields_ = [("offset", c_int64)] + [(n, c_int32) for n in ("H0", "W0", "i", "j", "h", "w", "flip", "reserved")]
 
 
+class RandaugRow(Structure):        # devias_randaug_row (ABI 180): 88 bytes
+    _fields_ = [("src", c_int64), ("dst", c_int64)] + [(n, c_int32) for n in ("H0", "W0", "op", "i0", "i1")] + [("f", c_float), ("a", c_double * 6)]
+
+
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2     # DEVIAS_MIX_*
 MIXUP_PAIRS_PER_LAUNCH = 32          # DEVIAS_MIXUP_PAIRS_PER_LAUNCH
 MIXUP_TARGET_ROWS_PER_LAUNCH = 256   # DEVIAS_MIXUP_TARGET_ROWS_PER_LAUNCH
 INGEST_ROWS_PER_LAUNCH = 32          # DEVIAS_INGEST_ROWS_PER_LAUNCH
 INGEST_MAX_SIDE = 16384              # DEVIAS_INGEST_MAX_SIDE
+RANDAUG_ROWS_PER_LAUNCH = 32         # DEVIAS_RANDAUG_ROWS_PER_LAUNCH
+RANDAUG_STATS_BYTES = 1024           # DEVIAS_RANDAUG_STATS_BYTES: per (clip, frame) three channel tables and the grey level
 DISTILL_KL, DISTILL_CE = 0, 1        # DEVIAS_DISTILL_KL / DEVIAS_DISTILL_CE
 POOL_MEAN, POOL_CLS = 0, 1           # DEVIAS_POOL_MEAN / DEVIAS_POOL_CLS
 POOL_HEAD_CHUNK = 64                 # DEVIAS_POOL_HEAD_CHUNK: token rows one workgroup of the region's streaming kernels covers
@@ -257,6 +263,9 @@ PROTOTYPES = {
     "devias_soft_ce_fwd": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "devias_soft_ce_bwd": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "devias_clip_ingest": (c_int, [_P, _L, _P, POINTER(IngestRow), _I, _I, _I, _I, _I, _P, _P]),
+    "devias_randaug_stats": (c_int, [_P, _L, POINTER(RandaugRow), _I, _I, _P, _P]),
+    "devias_randaug_apply": (c_int, [_P, _L, POINTER(RandaugRow), _I, _I, _P, _P]),
+    "devias_randaug_launches": (c_int64, []),
     "devias_agg_block_save_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_scratch_bytes": (c_int64, [POINTER(AggArgs)]),
     "devias_agg_block_workspace_bytes": (c_int64, [POINTER(AggArgs)]),

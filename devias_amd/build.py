@@ -22,7 +22,7 @@ GEMM_SOURCES = ["gemm256.hip", "gemm256p.hip", "gemm128_bf16.hip", "gemm128_f32.
 ATTN_SOURCES = ["attn_bwd1w.hip", "attn_mfma16.hip", "attn_fwd.hip", "attn_f32.hip", "attention.hip"]
 # the slot cross-attention: its kernel units (slot_common.h says which kernels share one) + the host side (slot_attn.hip); longest compile first (8.3 / 5.4 / 3.3 / 2.4 s each, alone)
 SLOT_SOURCES = ["slot_valu.hip", "slot_unfolded.hip", "slot_mfma.hip", "slot_attn.hip"]
-SOURCES = GEMM_SOURCES + ATTN_SOURCES + SLOT_SOURCES + ["layernorm.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "fusion_head.hip", "token_head.hip", "distill.hip", "mixup.hip", "ingest.hip", "probe.hip"]
+SOURCES = GEMM_SOURCES + ATTN_SOURCES + SLOT_SOURCES + ["layernorm.hip", "api.hip", "elementwise.hip", "loss.hip", "fame.hip", "regions.hip", "fusion_head.hip", "token_head.hip", "distill.hip", "mixup.hip", "ingest.hip", "randaug.hip", "probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HEADERS = ["common.h", "roctx_shim.h", "region_host.h", "row_kernels.h", "attn_common.h", "attn1w.h", "slot_common.h", "gemm_common.h", "gemm_tile256.h", "gemm128.h", "gemm256p.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wno-unused-result",
@@ -38,6 +38,8 @@ FILE_FLAGS = {src: ["-fno-slp-vectorize"] for src in ATTN_SOURCES}
 FILE_FLAGS["mixup.hip"] = ["-ffp-contract=off"]
 # the ingest rounds every product and sum of its bilinear interpolation on its own (an identity box returns the table's taps bit for bit): no contraction there either
 FILE_FLAGS["ingest.hip"] = ["-ffp-contract=off"]
+# RandAugment is Pillow's C arithmetic bit for bit: every fp32 and fp64 product and sum rounds on its own
+FILE_FLAGS["randaug.hip"] = ["-ffp-contract=off"]
 
 
 def _flags(src: str):

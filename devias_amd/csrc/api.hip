@@ -12,7 +12,7 @@ int devias_set_error(int code, const char* fmt, ...) {
     return code;
 }
 
-extern "C" int devias_version(void) { return 179; }   // 179: devias_clip_ingest (uint8 frames to normalised, cropped, resized, flipped clips; additive); 178: devias_mixup_clips / devias_mixup_target / devias_soft_ce_* (Mixup / CutMix on the device, soft-target cross-entropy; additive); 177: devias_two_token_head_* / devias_two_token_head_launches / devias_distill_* (the two-token multi-task baseline; additive); 176: devias_pool_head_* / devias_pool_head_launches (the plain video ViT's pooled-head region; additive); 175: devias_fusion_head_* / devias_softmax_ce_* / devias_region_counter (downstream fine-tuning; additive); 174: devias_adamw_step / devias_adamw_multi / devias_adamw_ema_multi take beta1, beta2 as double (recompile callers); 173: devias_encoder_block_infer (+ _workspace_bytes), DEVIAS_CNT_BLOCK_INFER (DEVIAS_CNT_MAX 25; additive); 172: devias_adamw_ema_multi, devias_ema_multi, devias_opt_tensor.ema (was reserved; additive); 171: devias_wgrad_group, devias_block_args.defer_wgrad / keep_*; 170: devias_option_name, option slot_mfma (additive); 169: launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM, DEVIAS_CNT_SLOTF_VALU, DEVIAS_CNT_SLOT; additive); 168: devias_head_match_loss_labels_fwd / _bwd (ground-truth scene labels; additive), DEVIAS_CNT_LOSS_LABELS; 167: devias_mhsa_*_flags (DEVIAS_ATTN_Q_PRESCALED), devias_block_args grew by WqkvS / qkv_biasS (recompile callers), option attn_qpre; 166: devias_block_args grew by the optional transposed weight copies W*T (recompile callers); 165: launch counters per dK / dV kernel form (DEVIAS_CNT_DKDV*, DEVIAS_CNT_MAX 24), option gemm_epi_spec (additive); 164: devias_mhsa_bwd uses its ws again (row statistics of the one-wave-per-SIMD dK / dV kernel), devias_mhsa_bwd_bias accepts dbv = NULL where devias_mhsa_bwd_bias_dv_from_do() says so; 163: devias_get_option, devias_gemm_release_queue_stream (additive); 162: devias_mhsa_bwd_bias (additive); 161: devias_mhsa_fwd_dropout / _bwd_dropout (additive); 160: devias_loss_dims.scene_ce (struct grew); 110: multi-tensor optimizer entry points, 120: devias_fame_*, 130: counters + options, 140: stream-K GEMM (args struct grew), 150: fused regions, roctx ranges
+extern "C" int devias_version(void) { return 180; }   // 180: devias_randaug_apply / devias_randaug_stats / devias_randaug_launches (RandAugment on the device; additive); 179: devias_clip_ingest (uint8 frames to normalised, cropped, resized, flipped clips; additive); 178: devias_mixup_clips / devias_mixup_target / devias_soft_ce_* (Mixup / CutMix on the device, soft-target cross-entropy; additive); 177: devias_two_token_head_* / devias_two_token_head_launches / devias_distill_* (the two-token multi-task baseline; additive); 176: devias_pool_head_* / devias_pool_head_launches (the plain video ViT's pooled-head region; additive); 175: devias_fusion_head_* / devias_softmax_ce_* / devias_region_counter (downstream fine-tuning; additive); 174: devias_adamw_step / devias_adamw_multi / devias_adamw_ema_multi take beta1, beta2 as double (recompile callers); 173: devias_encoder_block_infer (+ _workspace_bytes), DEVIAS_CNT_BLOCK_INFER (DEVIAS_CNT_MAX 25; additive); 172: devias_adamw_ema_multi, devias_ema_multi, devias_opt_tensor.ema (was reserved; additive); 171: devias_wgrad_group, devias_block_args.defer_wgrad / keep_*; 170: devias_option_name, option slot_mfma (additive); 169: launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM, DEVIAS_CNT_SLOTF_VALU, DEVIAS_CNT_SLOT; additive); 168: devias_head_match_loss_labels_fwd / _bwd (ground-truth scene labels; additive), DEVIAS_CNT_LOSS_LABELS; 167: devias_mhsa_*_flags (DEVIAS_ATTN_Q_PRESCALED), devias_block_args grew by WqkvS / qkv_biasS (recompile callers), option attn_qpre; 166: devias_block_args grew by the optional transposed weight copies W*T (recompile callers); 165: launch counters per dK / dV kernel form (DEVIAS_CNT_DKDV*, DEVIAS_CNT_MAX 24), option gemm_epi_spec (additive); 164: devias_mhsa_bwd uses its ws again (row statistics of the one-wave-per-SIMD dK / dV kernel), devias_mhsa_bwd_bias accepts dbv = NULL where devias_mhsa_bwd_bias_dv_from_do() says so; 163: devias_get_option, devias_gemm_release_queue_stream (additive); 162: devias_mhsa_bwd_bias (additive); 161: devias_mhsa_fwd_dropout / _bwd_dropout (additive); 160: devias_loss_dims.scene_ce (struct grew); 110: multi-tensor optimizer entry points, 120: devias_fame_*, 130: counters + options, 140: stream-K GEMM (args struct grew), 150: fused regions, roctx ranges
 
 // ---- launch counters: which kernel family served a call (tests assert that the measured kernels are the ones under test) ----
 #include <atomic>
@@ -27,6 +27,7 @@ extern "C" void devias_counters_reset(void) {
     for (int i = 0; i < DEVIAS_RCNT_MAX; ++i) g_rcnt[i].store(0, std::memory_order_relaxed);
     devias_pool_head_counter_reset();
     devias_two_token_head_counter_reset();
+    devias_randaug_counter_reset();
 }
 
 // ---- process-wide options: the table of common.h, its values read from the environment ONCE, changeable at run time (tests, A/B tools) ----

@@ -22,7 +22,8 @@ void devias_count(int id);                                  // launch counters (
 void devias_count_region(int id);                           // the second bank (api.hip): DEVIAS_RCNT_*, calls per fused region / loss entry point
 void devias_pool_head_counter_reset();                      // token_head.hip: the call counter behind devias_pool_head_launches (both banks are closed); devias_counters_reset calls it
 void devias_two_token_head_counter_reset();                 // token_head.hip: the call counter behind devias_two_token_head_launches; devias_counters_reset calls it
-extern "C" int32_t devias_policy_gemm_cus(void);             // gemm.hip (the GEMM's host side): CUs the big-tile grids count on (device CUs - option gemm_reserve_cus)
+void devias_randaug_counter_reset();                        // randaug.hip: the launch counter behind devias_randaug_launches; devias_counters_reset calls it
+extern "C" int32_t devias_policy_gemm_cus(void);            // gemm.hip (the GEMM's host side): CUs the big-tile grids count on (device CUs - option gemm_reserve_cus)
 
 // ---- process-wide options ----------------------------------------------------------------------------------------------------------------
 // ONE row per option: (id, name for devias_set_option / devias_get_option, environment variable read once at first use, default).  What each value

@@ -3,8 +3,9 @@
 or the view's window, ClipToTensor, Normalize.  The frames cross the bus as uint8 (a quarter of the fp32 clip) and ONE kernel launch (devias_clip_ingest) writes the clip.
 
 The draws are the reference's, on the host, from Python's `random` and numpy's global state in the reference's order and amount (ClipIngest.draw); the boxes reach the
-device as kernel arguments.  Out of scope: decoding, RandAugment (PIL on uint8, before the ingest), the short-side Resize of validation / test (the worker's antialiased
-uint8 resize), motion_shift, random erasing, FastCollateMixup."""
+device as kernel arguments.  RandAugment, which the reference runs on the uint8 frames before all of this, is devias_amd.randaug's: IngestLoader(..., randaug=...) draws
+its plan before each clip's box and runs it on the staged buffer that the ingest then reads.  Out of scope: decoding, the short-side Resize of validation / test (the
+worker's antialiased uint8 resize), motion_shift, random erasing, FastCollateMixup."""
 from __future__ import annotations
 
 import math
@@ -55,6 +56,21 @@ def ingest_cpu(frames: torch.Tensor, box: Box, table: torch.Tensor, S_h: int, S_
     p = wx0 * top[..., c0] + lx * top[..., c1]
     q = wx0 * bot[..., c0] + lx * bot[..., c1]
     return (wy0 * p + ly * q).to(out_dtype)
+
+
+def check_clips(frames, who: str = "ClipIngest"):
+    """the clips of a batch given as uint8 [B, T, H0, W0, 3] or as a list of B tensors [T, H0_b, W0_b, 3] -> (list of clips, T)"""
+    clips: List[torch.Tensor] = list(frames) if isinstance(frames, (list, tuple)) else None
+    if clips is None:
+        if not (isinstance(frames, torch.Tensor) and frames.dim() == 5):
+            raise ValueError(f"{who}: uint8 frames [B, T, H0, W0, 3] or a list of B tensors [T, H0, W0, 3] expected")
+        clips = list(frames.unbind(0))
+    if not clips or any(not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 4 or c.shape[3] != 3 or c.numel() == 0 for c in clips):
+        raise ValueError(f"{who}: every clip is a non-empty uint8 tensor [T, H0, W0, 3]")
+    T = clips[0].shape[0]
+    if any(c.shape[0] != T for c in clips) or len({c.device for c in clips}) != 1:
+        raise ValueError(f"{who}: the clips of a batch share T and the device")
+    return clips, T
 
 
 class ClipIngest:
@@ -141,8 +157,9 @@ class ClipIngest:
             self._tables[key] = self.table.to(device)
         return self._tables[key]
 
-    def _stage(self, clips: Sequence[torch.Tensor], nbytes: int, device) -> torch.Tensor:
-        """the host clips packed back to back into the next pinned buffer of the ring and copied to a fresh device buffer with one non_blocking transfer"""
+    def _stage(self, clips: Sequence[torch.Tensor], nbytes: int, device, alloc: Optional[int] = None) -> torch.Tensor:
+        """the host clips packed back to back into the next pinned buffer of the ring and copied to a fresh device buffer with one non_blocking transfer; alloc: the
+        device buffer's size where it is to be larger than the clips (RandAugment's double-sized buffer: the clips fill its lower part)"""
         s = self._slot
         self._slot = (s + 1) % self.RING
         if self._events[s] is not None:
@@ -154,8 +171,8 @@ class ClipIngest:
             n = c.numel()
             host[off:off + n].view(c.shape).copy_(c)
             off += n
-        dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        dev.copy_(host[:nbytes], non_blocking=True)
+        dev = torch.empty(max(nbytes, int(alloc or 0)), dtype=torch.uint8, device=device)
+        dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._events[s] = ev
@@ -174,16 +191,7 @@ class ClipIngest:
         return ops.clip_ingest(buf, self._table_on(buf.device), rows, int(T), out)
 
     def __call__(self, frames, boxes: Optional[Sequence[Box]] = None) -> torch.Tensor:
-        clips: List[torch.Tensor] = list(frames) if isinstance(frames, (list, tuple)) else None
-        if clips is None:
-            if not (isinstance(frames, torch.Tensor) and frames.dim() == 5):
-                raise ValueError("ClipIngest: uint8 frames [B, T, H0, W0, 3] or a list of B tensors [T, H0, W0, 3] expected")
-            clips = list(frames.unbind(0))
-        if not clips or any(not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 4 or c.shape[3] != 3 or c.numel() == 0 for c in clips):
-            raise ValueError("ClipIngest: every clip is a non-empty uint8 tensor [T, H0, W0, 3]")
-        T = clips[0].shape[0]
-        if any(c.shape[0] != T for c in clips) or len({c.device for c in clips}) != 1:
-            raise ValueError("ClipIngest: the clips of a batch share T and the device")
+        clips, T = check_clips(frames)
         if boxes is None:
             boxes = [self.draw(c.shape[1], c.shape[2]) for c in clips]
         if len(boxes) != len(clips):
@@ -211,12 +219,17 @@ class IngestLoader:
     """Wraps any loader whose field 0 is uint8 frames ([B, T, H0, W0, 3] or a list of [T, H0_b, W0_b, 3]) and yields the same batches with field 0 replaced by the
     device clip; every other field passes through untouched.  The engines are not edited: their `.to(device)` on a tensor that is already there is a no-op.
     mode "train": boxes and flips drawn per clip, in batch order (ClipIngest.draw); "center": the validation CenterCrop; "test": the view's window, with split_nb read
-    from field 4 of the batch, where the reference's test dataset puts it (buffer, label, name, chunk_nb, split_nb), and num_crop views per video."""
+    from field 4 of the batch, where the reference's test dataset puts it (buffer, label, name, chunk_nb, split_nb), and num_crop views per video.
+    randaug (mode "train" only): a devias_amd.randaug.RandAugment.  The draws are then made clip by clip in the reference's order (_aug_frame): the clip's RandAugment
+    plan, then its box and flip.  The frames are staged once, into the lower half of a double-sized buffer; the layers run in that buffer and the ingest reads the
+    clips where the last layer left them.  Without it the draws and the path are what they were."""
 
-    def __init__(self, data_loader, ingest: ClipIngest, mode: str = "train", num_crop: int = 3):
+    def __init__(self, data_loader, ingest: ClipIngest, mode: str = "train", num_crop: int = 3, randaug=None):
         if mode not in ("train", "center", "test"):
             raise ValueError(f"IngestLoader: mode {mode!r}")
-        self.data_loader, self.ingest, self.mode, self.num_crop = data_loader, ingest, mode, int(num_crop)
+        if randaug is not None and mode != "train":
+            raise ValueError(f"IngestLoader: RandAugment belongs to training; mode {mode!r} takes no randaug")
+        self.data_loader, self.ingest, self.mode, self.num_crop, self.randaug = data_loader, ingest, mode, int(num_crop), randaug
 
     def __len__(self):
         return len(self.data_loader)
@@ -234,9 +247,34 @@ class IngestLoader:
         split = split.tolist() if isinstance(split, torch.Tensor) else list(split)
         return [self.ingest.test_box(H0, W0, int(s), self.num_crop) for (H0, W0), s in zip(sizes, split)]
 
+    def _augmented(self, frames) -> torch.Tensor:
+        """RandAugment, then the ingest: plan and box drawn per clip, in that order"""
+        ra, m = self.randaug, self.ingest
+        clips, T = check_clips(frames, "IngestLoader")
+        plans, boxes = [], []
+        for c in clips:
+            plans.append(ra.draw())
+            boxes.append(m.draw(c.shape[1], c.shape[2]))
+        src_dev = clips[0].device
+        device = src_dev if src_dev.type != "cpu" else m.device
+        if device.type == "cpu":
+            from .randaug import randaug_cpu
+            return m([randaug_cpu(c, p, ra.resample) for c, p in zip(clips, plans)], boxes)
+        sizes = [c.numel() for c in clips]
+        offsets = [0] + [int(v) for v in np.cumsum(sizes)[:-1]]
+        nbytes, half = int(sum(sizes)), ra.half_of(sum(sizes))
+        if src_dev.type == "cpu":
+            buf = m._stage(clips, nbytes, device, alloc=2 * half)
+        else:                                                # device frames are the caller's: the layers run on a copy
+            buf = torch.empty(2 * half, dtype=torch.uint8, device=device)
+            for c, o, n in zip(clips, offsets, sizes):
+                buf[o:o + n].view(c.shape).copy_(c)
+        buf, layout = ra.augment_buffer(buf, T, [(o, c.shape[1], c.shape[2]) for o, c in zip(offsets, clips)], plans)
+        return m.ingest_buffer(buf, T, layout, boxes)
+
     def __iter__(self):
         for batch in self.data_loader:
             if not isinstance(batch, (list, tuple)):
                 raise TypeError(f"IngestLoader: a batch is a list or tuple whose field 0 holds the uint8 frames, got {type(batch).__name__}")
-            clip = self.ingest(batch[0], self._boxes(batch, batch[0]))
+            clip = self._augmented(batch[0]) if self.randaug is not None else self.ingest(batch[0], self._boxes(batch, batch[0]))
             yield type(batch)([clip] + list(batch[1:]))

@@ -294,6 +294,36 @@ def clip_ingest(src: torch.Tensor, table: torch.Tensor, rows, T: int, out: torch
     return out
 
 
+def _chk_randaug(who, buf, rows, T, stats):
+    _chk(buf, who + ".buf", torch.uint8)
+    _chk(stats, who + ".stats", torch.uint8)
+    if buf.dim() != 1 or stats.dim() != 1 or stats.numel() < len(rows) * int(T) * _lib.RANDAUG_STATS_BYTES:
+        raise ValueError(f"{who}: a flat buf and flat stats of at least B * T * {_lib.RANDAUG_STATS_BYTES} = {len(rows) * int(T) * _lib.RANDAUG_STATS_BYTES} bytes expected, "
+                         f"got {tuple(buf.shape)} and {tuple(stats.shape)}")
+
+
+def randaug_stats(buf: torch.Tensor, rows, T: int, stats: torch.Tensor) -> torch.Tensor:
+    """devias_randaug_stats: the tables / grey levels that the AutoContrast, Equalize and Contrast rows of one layer need, into stats (flat uint8, B * T *
+    _lib.RANDAUG_STATS_BYTES); rows a ctypes array of B _lib.RandaugRow (host memory: the rows travel as kernel arguments)"""
+    _chk_randaug("randaug_stats", buf, rows, T, stats)
+    _lib.check(_lib.load().devias_randaug_stats(buf.data_ptr(), buf.numel(), rows, len(rows), int(T), stats.data_ptr(), _stream()), "devias_randaug_stats")
+    return stats
+
+
+def randaug_apply(buf: torch.Tensor, rows, T: int, stats: torch.Tensor) -> torch.Tensor:
+    """devias_randaug_apply: one RandAugment layer on the clips of the flat uint8 device buffer `buf`, IN the buffer: every row's op reads its clip at row.src and
+    writes it at row.dst (the same place for a point op)"""
+    _chk_randaug("randaug_apply", buf, rows, T, stats)
+    _lib.check(_lib.load().devias_randaug_apply(buf.data_ptr(), buf.numel(), rows, len(rows), int(T), stats.data_ptr(), _stream()), "devias_randaug_apply")
+    return buf
+
+
+def randaug_launches() -> int:
+    """kernel launches of devias_randaug_stats / devias_randaug_apply since the last reset (devias_randaug_launches: a counter of its own, both banks are closed);
+    counters(reset=True) resets it"""
+    return int(_lib.load().devias_randaug_launches())
+
+
 def _chk_soft_ce(who, logits, target):
     _chk(logits, who + ".logits")
     _chk(target, who + ".target", torch.float32)

@@ -58,6 +58,7 @@ int devias_version(void);          /* 100 + additions: 110 = multi-tensor optimi
                                     177 = devias_two_token_head_* (the multi-task baseline's two-token head region), devias_two_token_head_launches, devias_distill_* (additive),
                                     178 = devias_mixup_clips, devias_mixup_target (Mixup / CutMix on the device), devias_soft_ce_* (SoftTargetCrossEntropy) (additive),
                                     179 = devias_clip_ingest (clip ingest on the device: uint8 frames to normalised, cropped, resized, flipped clips) (additive),
+                                    180 = devias_randaug_apply, devias_randaug_stats, devias_randaug_launches (RandAugment on the device: the recipe's 15 PIL ops on uint8 clips) (additive),
                                     169 = launch counters per slot-attention kernel family (DEVIAS_CNT_SLOTM / _SLOTF_VALU / _SLOT; additive) */
 const char* devias_last_error(void);
 /* Launch counters: one per kernel family, incremented by the host side of each entry point (process-wide, relaxed atomics).
@@ -906,6 +907,68 @@ typedef struct {
 } devias_ingest_row;                     /* 40 bytes */
 int devias_clip_ingest(const void* src, int64_t src_bytes, const float* table, const devias_ingest_row* rows, int32_t B, int32_t T, int32_t S_h, int32_t S_w,
                        int32_t out_dtype, void* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * ABI 180: RandAugment on the device -- the 15 PIL operations of the reference's recipe (utils/transform/rand_augment.py behind video_transforms.create_random_augment,
+ * `--aa rand-m7-n4-mstd0.5-inc1 --train_interpolation bicubic`) on the uint8 frames [T, H0, W0, 3] of B clips in one flat DEVICE buffer, bit for bit Pillow's results.
+ * The host draws the plan and turns each applied layer into ONE row per clip (devias_amd/randaug.py: lower); a clip whose layer was skipped or is an identity (a
+ * rotation by 0, an enhance factor of 1.0, a posterize that keeps 8 bits) gets DEVIAS_RA_NONE and is neither launched over nor copied.
+ *
+ * devias_randaug_apply: one layer.  One launch per DEVIAS_RANDAUG_ROWS_PER_LAUNCH rows whose op is not DEVIAS_RA_NONE, none where there is no such row; the op is
+ * uniform per workgroup.  Point ops work in place (dst == src); the neighbourhood ops (Sharpness, the affine ops) read the clip at src and write it at dst, a run
+ * of the same buffer apart from src.  u, v: bytes of a pixel before / after; every fp32 and fp64 product and sum rounds on its own (no contraction):
+ *   INVERT        v = 255 - u                                           POSTERIZE     v = u & i0   (i0 = ~(2^(8 - bits) - 1) & 255)
+ *   SOLARIZE      v = u < i0 ? u : 255 - u                              SOLARIZE_ADD  v = u < i1 ? min(255, u + i0) : u
+ *   AUTOCONTRAST, EQUALIZE   v = table[frame][channel][u], the tables devias_randaug_stats built
+ *   blend(d, u)   t = fl32(d + fl32(f * (u - d))); v = trunc(t) for f in [0, 1], else t <= 0 ? 0 : t >= 255 ? 255 : trunc(t)          (Image.blend)
+ *   BRIGHTNESS    d = 0          CONTRAST  d = the frame's grey level (devias_randaug_stats)          COLOR  d = L(pixel) = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16
+ *   SHARPNESS     d = the 3 x 3 smooth of the frame: border pixels copied; inside s = 0.5f, then for the rows y + 1, y, y - 1 in this order
+ *                 s = fl32(s + fl32(fl32(fl32(u[x-1] k0) + fl32(u[x] k1)) + fl32(u[x+1] k2))), k = (1, 1, 1, 1, 5, 1, 1, 1, 1) / 13 in fp32; d = clamp(trunc(s))
+ *   AFFINE        for output pixel (x, y): xin = fl(fl(fl(a0 (x + 0.5)) + fl(a1 (y + 0.5))) + a2), yin likewise with a3..a5, fp64; outside [0, W0) x [0, H0): (128, 128, 128).
+ *                 Else xin -= 0.5, yin -= 0.5, the floors and d = the fractions.  i0 = DEVIAS_RA_BICUBIC: four taps per axis at floor - 1 .. floor + 2, clamped to the
+ *                 frame, each axis p1 + d (p2 + d (p3 + d p4)), p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4 (columns first);
+ *                 DEVIAS_RA_BILINEAR: two taps, a + (b - a) d.  v <= 0 ? 0 : v >= 255 ? 255 : trunc(v).
+ * devias_randaug_stats: the statistics a layer's AUTOCONTRAST, EQUALIZE and CONTRAST rows need, one launch per DEVIAS_RANDAUG_ROWS_PER_LAUNCH such rows, none where
+ * there is none; called before that layer's devias_randaug_apply with the same rows, on the same stream.  Per frame t of clip b, at stats + (b T + t)
+ * DEVIAS_RANDAUG_STATS_BYTES: bytes [0, 768) the three channel tables, bytes [768, 772) the int32 grey level.  From the 256-bin histogram h of a channel:
+ *   AUTOCONTRAST  lo, hi the first and last non-empty bin; hi <= lo: identity; else scale = 255.0 / (hi - lo), offset = -lo scale, table[ix] = clamp(trunc(fl(fl(ix scale) + offset))), fp64
+ *   EQUALIZE      step = (sum h - the last non-empty bin) / 255 (integers; 0 where one bin holds everything): 0: identity; else n = step / 2, table[i] = min(255, n / step), n += h[i]
+ *   CONTRAST      grey = trunc(sum L / (H0 W0) + 0.5) in fp64 from the integer sum of the frame's luminances
+ * The sums are integers (LDS atomics): any order gives the same bits.  The host reads nothing back.
+ * `rows` is HOST memory, read before the call returns (kernel arguments: no copy, no synchronisation).  stats: B T DEVIAS_RANDAUG_STATS_BYTES bytes of DEVICE memory,
+ * may be NULL where no row needs statistics.
+ * Checked before any launch, by both (DEVIAS_EINVAL): null buf / rows; B, T < 1; an unknown op; and for every row but DEVIAS_RA_NONE: a side < 1 or above
+ * DEVIAS_INGEST_MAX_SIDE; T H0 W0 >= 2^31; src (dst) + T H0 W0 3 beyond `bytes`; a point op with dst != src; a neighbourhood op whose dst run meets its src run; runs
+ * of two rows that meet; a non-finite f or a[]; a resampling code other than the two; i0 / i1 outside the table's domain; statistics needed and stats NULL.
+ * devias_randaug_launches(): kernel launches of both entry points since the last devias_counters_reset() (a counter of its own: both banks are closed).
+ * ------------------------------------------------------------------------------------------------- */
+#define DEVIAS_RANDAUG_ROWS_PER_LAUNCH 32
+#define DEVIAS_RANDAUG_STATS_BYTES 1024
+#define DEVIAS_RA_NONE 0
+#define DEVIAS_RA_AUTOCONTRAST 1
+#define DEVIAS_RA_EQUALIZE 2
+#define DEVIAS_RA_INVERT 3
+#define DEVIAS_RA_POSTERIZE 4
+#define DEVIAS_RA_SOLARIZE 5
+#define DEVIAS_RA_SOLARIZE_ADD 6
+#define DEVIAS_RA_COLOR 7
+#define DEVIAS_RA_CONTRAST 8
+#define DEVIAS_RA_BRIGHTNESS 9
+#define DEVIAS_RA_SHARPNESS 10
+#define DEVIAS_RA_AFFINE 11
+#define DEVIAS_RA_BILINEAR 2             /* PIL's resampling codes */
+#define DEVIAS_RA_BICUBIC 3
+typedef struct {
+    int64_t src, dst;                    /* byte offsets of the clip's [T, H0, W0, 3] frames in buf: where the layer reads and where it writes them */
+    int32_t H0, W0;                      /* the frames' size */
+    int32_t op;                          /* DEVIAS_RA_* */
+    int32_t i0, i1;                      /* the posterize mask / the solarize threshold / SolarizeAdd's add and threshold / the affine ops' resampling code */
+    float f;                             /* the enhance factor, as Image.blend receives it */
+    double a[6];                         /* the affine coefficients */
+} devias_randaug_row;                    /* 88 bytes */
+int devias_randaug_stats(const void* buf, int64_t bytes, const devias_randaug_row* rows, int32_t B, int32_t T, void* stats, void* stream);
+int devias_randaug_apply(void* buf, int64_t bytes, const devias_randaug_row* rows, int32_t B, int32_t T, const void* stats, void* stream);
+int64_t devias_randaug_launches(void);
 
 /* Final LayerNorm + AggregationBlock with the folded slot attention (modeling_slot.py:373,381; agg_block/agg_block.py:105-139;
  * agg_block/attention.py:29-40,66-72,108-141): `depth` layers over `tied ? 1 : depth` weight sets; S <= 4 slots. */
